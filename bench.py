@@ -2,14 +2,23 @@
 """bench.py -- images/sec of the MVAE train step on N MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload mnist|fashionmnist|celeba|celeba19]
-                    [--batch B_PER_GPU]
+                    [--batch B_PER_GPU] [--dump-outputs DIR] [--full]
 
 One "step" = zero_grad -> the three (celeba19: 20+M) ELBO terms forward -> backward ->
 [gradient all-reduce] -> Adam, on a synthetic random-pixel / random-label batch that is already
 resident in HBM.  Default workload = BASELINE.json configs[1]: MNIST MVAE,
 n-latents 64, batch 512 per GPU.  Weak scaling: the per-GPU batch is fixed as N grows.
 
-Prints ONE JSON line (rank 0).  Besides the contract fields it carries
+A plain run does only what the headline needs: set up and capture, SETTLE_STEPS untimed steps, W untimed warm-up
+steps, exactly K timed steps, and ONE JSON line (rank 0) with the contract fields and `ms_per_step` (one timed step).
+--dump-outputs DIR  after the timed steps, writes what the last timed step computed (`elbo` as replay() returns it,
+                    the parameters, their gradients and the buffers after it) as DIR/<name>.npy, float32 / float64,
+                    a fixed seeded sample where the whole would pass DUMP_BUDGET_BYTES; inputs are seeded, so two
+                    builds can be compared output for output.
+--full              everything else the line has carried, measured as before (it takes ~90 s on the default workload):
+  step_distribution -- the settle pass becomes max(50, K) steps with one HIP event between consecutive steps,
+                   ms_per_step_median / p90 come from it,
+Besides the contract fields a --full line carries
   roofline      -- the dominant GEMM-shaped call of the step, IN SITU: every launcher is bracketed by HIP
                    events on the launch stream (profiler.KernelProfile) and eager single-stream steps are
                    enqueued behind a spin kernel that outlasts the host's enqueue time, so an interval
@@ -24,13 +33,13 @@ Prints ONE JSON line (rank 0).  Besides the contract fields it carries
                    host cores of this box on a bounded sample of the same workload; ``cores`` = intra-op
                    threads used (fastest of a few counts), ``host`` = nproc + CPU model,
                    ``cfg0_mnist_b128`` = BASELINE configs[0], ``elbo_delta`` = HIP vs oracle on one step,
-  dist          -- (N > 1 or --force-dp) world size, backend + RCCL version, an all-reduce-of-ones check,
-                   bucket sizes, ms/step of the same launch path with the collectives switched off and
-                   the difference (= exposed communication),
-  also          -- (default invocation only) the CelebA B=256 step: images/sec and the fp32-MFMA
+  dist          -- (N > 1 or --force-dp) ms/step of the same launch path with the collectives switched off and
+                   the difference (= exposed communication); world size, backend + RCCL version, the
+                   all-reduce-of-ones check, transport and bucket sizes are on every data-parallel line,
+  also          -- (MNIST at its default batch only) the CelebA B=256 step: images/sec and the fp32-MFMA
                    roofline of its conv kernels, the figure north_star's 40 % target is about.
-Flags beyond the contract: --no-extras (value only), --no-graph, --force-dp (world-1 run through the
-data-parallel launch path), --force-tiling wm,wn[,splits] (tuning build of the library).
+Flags beyond the contract: --no-extras (with --full: step_distribution / dist only), --no-graph, --force-dp
+(world-1 run through the data-parallel launch path), --force-tiling wm,wn[,splits] (tuning build of the library).
 """
 import argparse
 import json
@@ -48,6 +57,10 @@ DEFAULT_BATCH = {'mnist': 512, 'fashionmnist': 1024, 'celeba': 256, 'celeba19': 
 LAMBDA_LABEL = {'mnist': 50.0, 'fashionmnist': 50.0, 'celeba': 10.0, 'celeba19': 10.0}
 N_LATENTS = {'mnist': 64, 'fashionmnist': 64, 'celeba': 100, 'celeba19': 100}
 LR = {'mnist': 1e-3, 'fashionmnist': 1e-3, 'celeba': 1e-4, 'celeba19': 1e-4}
+# untimed steps between the capture and the warm-up of a plain run (the first tens of replays after a capture are slower)
+SETTLE_STEPS = 50
+# --dump-outputs writes at most this much (the contract allows 64 MB); larger models are sampled, see dump_outputs()
+DUMP_BUDGET_BYTES = 60 << 20
 
 
 def synthetic(kind, batch, seed, device):
@@ -82,7 +95,37 @@ def annealing(step, total=2000):
     return min(1.0, float(step + 1) / total)
 
 
-def timed_run(kind, batch, steps, warmup, device, world, rank, use_graph=True, force_dp=False, faithful_bn_stats=True):
+def dump_outputs(out_dir, model, elbo):
+    """What the last timed step handed its caller: ``elbo`` as replay() / step() returned it, every parameter, its
+    gradient (the gradient arena: ``p.grad`` may be None between steps) and every buffer, as ``<name>.npy`` (float32;
+    integer buffers as float64).  If the whole would pass DUMP_BUDGET_BYTES, arrays of up to 4096 elements stay whole and
+    every larger one keeps the same fraction of its elements at sorted positions drawn by a generator seeded with 0 --
+    fixed by the shapes alone, so two builds of the project sample the same elements."""
+    import numpy as np
+    arrays = [('elbo', elbo)]
+    params = dict(model.named_parameters())
+    for name, p in params.items():
+        arrays.append(('param.' + name, p))
+        arena = getattr(p, '_arena', None)
+        arrays.append(('grad.' + name, arena.grad_view(p) if arena is not None else p.grad))
+    for name, b in model.state_dict().items():          # state_dict() flushes the lazily counted num_batches_tracked
+        if name not in params:
+            arrays.append(('buffer.' + name, b))
+    arrays = [(n, t.detach().cpu().numpy()) for n, t in arrays if t is not None]
+    arrays = [(n, a.astype(np.float32 if a.dtype.kind == 'f' and a.itemsize <= 4 else np.float64)) for n, a in arrays]
+    small = sum(a.nbytes for _, a in arrays if a.size <= 4096)
+    large = sum(a.nbytes for _, a in arrays if a.size > 4096)
+    frac = min(1.0, (DUMP_BUDGET_BYTES - small) / float(max(large, 1)))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays:
+        if frac < 1.0 and a.size > 4096:
+            k = max(1, int(a.size * frac))
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
+def timed_run(kind, batch, steps, warmup, device, world, rank, use_graph=True, force_dp=False, faithful_bn_stats=True,
+              full=True, dump_dir=None):
     import torch.distributed as dist
     model, eng, opt = build(kind, batch, device, world, faithful_bn_stats=faithful_bn_stats)
     dp = None
@@ -132,9 +175,11 @@ def timed_run(kind, batch, steps, warmup, device, world, rank, use_graph=True, f
     # where `--steps 100 --warmup 20` reads 0.274-0.276 -- the first tens of replays after a capture are slower (clocks,
     # caches, first launches of a new graph).  The events of the distribution pass are not inside the region `value` comes from.
     # At world > 1 the same number of steps runs untimed (no events): N = 1 and N > 1 lines are taken in the same state.
-    n_pre = max(50, steps)
+    # Without `full` (a plain run) the pass is SETTLE_STEPS untimed steps, no events: only what keeps the region out of
+    # the post-capture transient.
+    n_pre = max(50, steps) if full else SETTLE_STEPS
     dist_steps = None
-    if device.type == 'cuda' and world == 1:
+    if full and device.type == 'cuda' and world == 1:
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_pre + 1)]
         torch.cuda.synchronize(device)
         for i in range(n_pre):
@@ -152,11 +197,15 @@ def timed_run(kind, batch, steps, warmup, device, world, rank, use_graph=True, f
     for i in range(warmup):
         one(n_pre + i)
     dt, elbo = timed(steps, n_pre + warmup)
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, model, elbo)
     info = None
     if dp is not None:
+        sizes = [(hi - lo) * 4 for lo, hi in dp.buckets.ranges]
+        info = {'bucket_bytes': sizes, 'transport': dp.transport}
+    if dp is not None and full:
         # what the data-parallel exchange costs: the same launch path with the collectives switched off
         # (replicas diverge from here on -- nothing is measured after this)
-        sizes = [(hi - lo) * 4 for lo, hi in dp.buckets.ranges]
         dp.buckets.launch = lambda k: None
         dp.buckets.wait = lambda k=None: None
         if use_graph and dp.in_graph:
@@ -164,9 +213,8 @@ def timed_run(kind, batch, steps, warmup, device, world, rank, use_graph=True, f
             eng.capture(opt, batches[0][0].shape[1:], batches[0][1], comm=dp)
         n2 = max(5, steps // 2)
         dt_off, _ = timed(n2, n_pre + warmup + steps)
-        info = {'bucket_bytes': sizes, 'transport': dp.transport,
-                'ms_per_step_without_collectives': round(dt_off / n2 * 1e3, 4),
-                'exposed_comm_ms_per_step': round((dt / steps - dt_off / n2) * 1e3, 4)}
+        info.update({'ms_per_step_without_collectives': round(dt_off / n2 * 1e3, 4),
+                     'exposed_comm_ms_per_step': round((dt / steps - dt_off / n2) * 1e3, 4)})
     loss = float(elbo[-1].item())
     return dt, loss, (model, eng, opt, batches, info, dist_steps)
 
@@ -627,7 +675,12 @@ def main():
     ap.add_argument('--no-graph', action='store_true')
     ap.add_argument('--force-tiling', default=None,
                     help='tuning aid: wm,wn,splits,kwaves forwarded to mvae_debug_set_tiling / _kwaves')
-    ap.add_argument('--no-extras', action='store_true', help='skip roofline / cpu_baseline / also')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip roofline / cpu_baseline / also')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: step distribution, roofline, cpu_baseline, '
+                         'module_surface, the other workloads (`also`), exposed communication')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help="write the last timed step's outputs (ELBO terms, parameters, gradients, buffers) as DIR/<name>.npy")
     ap.add_argument('--force-dp', action='store_true',
                     help='tuning aid: run the data-parallel launch path (3 graphs + RCCL) even at world size 1')
     ap.add_argument('--backend', default='nccl', choices=('nccl', 'gloo'),
@@ -724,7 +777,8 @@ def main():
         return
 
     dt, loss, state = timed_run(kind, batch, args.steps, args.warmup, device, world, rank,
-                                use_graph=not args.no_graph, force_dp=args.force_dp)
+                                use_graph=not args.no_graph, force_dp=args.force_dp, full=args.full,
+                                dump_dir=args.dump_outputs)
     out = {
         'metric': 'images/sec (MVAE train step)', 'value': round(world * batch * args.steps / dt, 1),
         'unit': 'images/sec', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -735,13 +789,14 @@ def main():
                    'global_batch': world * batch, 'parallelism': 'dp%d' % world,
                    'launch': 'eager' if args.no_graph else 'hipGraph replay', 'final_loss': round(loss, 3),
                    'value_from': 'the contract region: --warmup untimed steps, then exactly --steps steps between two barrier + '
-                                 'synchronize fences (max over ranks).  It runs BEHIND a separate pass of max(50, steps) steps (at N = 1 '
-                                 'with one HIP event per step: ms_per_step_median / p90 come from that pass), so that a short region '
-                                 'is not taken in the first milliseconds after the graph capture'},
+                                 'synchronize fences (max over ranks).  It runs BEHIND a separate pass of %s steps (%s), so that a '
+                                 'short region is not taken in the first milliseconds after the graph capture' % (
+                                     ('max(50, steps)', 'at N = 1 with one HIP event per step: ms_per_step_median / p90 come '
+                                      'from that pass') if args.full else (str(SETTLE_STEPS), 'untimed'))},
     }
     if state[4] is not None:
         out['dist'] = dict(dist_info, **state[4])
-        if rank == 0:
+        if rank == 0 and 'exposed_comm_ms_per_step' in out['dist']:
             sys.stderr.write('[bench] world %d over %s (RCCL %s); all-reduce of ones = %g; buckets %s bytes; '
                              'exposed communication %.4f ms/step\n' % (
                                  out['dist']['world_size'], out['dist']['backend'], out['dist'].get('rccl_version'),
@@ -750,7 +805,7 @@ def main():
     if state[5] is not None:
         out.update({k: state[5][k] for k in ('ms_per_step_median', 'ms_per_step_p90')})
         out['step_distribution'] = state[5]
-    if rank == 0 and world == 1 and not args.no_extras and not args.force_dp:
+    if rank == 0 and world == 1 and args.full and not args.no_extras and not args.force_dp:
         model, eng, opt, batches = state[:4]
         out['roofline'] = roofline_from_profile(eng, opt, batches, kind=kind)
         out['cpu_baseline'] = cpu_baseline(kind, batch)

@@ -8,7 +8,7 @@ if [ "$1" != "notests" ]; then
     grep -E "passed|failed" $out/tests.log | tail -2 >> $out/status.txt
     timeout 200 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1; echo "smoke rc=$?" >> $out/status.txt
 fi
-timeout 400 python bench.py > $out/r02_bench_default.json 2> $out/bench.err; echo "bench rc=$?" >> $out/status.txt
+timeout 400 python bench.py --full > $out/r02_bench_default.json 2> $out/bench.err; echo "bench rc=$?" >> $out/status.txt
 bash tools/collect_profiles.sh > $out/collect_profiles.log 2>&1
 cp gpurun_out/profiles_new/r02_*_kernel_stats.txt $out/ 2>/dev/null
 python tools/gemm_bench.py --cases all 2>&1 | grep -v amdgpu.ids > $out/r02_gemm_bench.txt

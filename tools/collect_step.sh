@@ -4,7 +4,7 @@
 # (of which only the optimizer tests run).            -> gpurun_out/final/
 cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/final; rm -rf $out; mkdir -p $out
-timeout 100 python bench.py > $out/r02_bench_default.json 2> $out/bench.err; echo "bench rc=$?" > $out/status.txt
+timeout 100 python bench.py --full > $out/r02_bench_default.json 2> $out/bench.err; echo "bench rc=$?" > $out/status.txt
 bash tools/collect_profiles.sh > $out/collect_profiles.log 2>&1
 cp gpurun_out/profiles_new/r02_*_kernel_stats.txt $out/ 2>/dev/null
 timeout 60 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1; echo "smoke rc=$?" >> $out/status.txt

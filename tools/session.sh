@@ -26,7 +26,7 @@ final)
         "linear_dgrad|M1024 N512 K512" "convT2d_fwd|2048x64x14x14" "convT2d_dgrad|512x256x5x5" "convT2d_dgrad|2048x128x7x7" \
         "convT2d_fwd|4608x128x8x8" "convT2d_wgrad|256x128x4x4" > $out/traffic.log 2>&1
     cp gpurun_out/${PFX}_traffic.json $out/ 2>/dev/null; cp gpurun_out/${PFX}_traffic.json profiles/${PFX}_traffic.json 2>/dev/null
-    t0=$(date +%s); timeout 900 python bench.py > $out/${PFX}_bench_default.json 2> $out/bench.err
+    t0=$(date +%s); timeout 900 python bench.py --full > $out/${PFX}_bench_default.json 2> $out/bench.err
     echo "bench rc=$? wall=$(( $(date +%s) - t0 ))s" >> $out/status.txt
     timeout 900 bash tools/collect_profiles.sh > $out/collect_profiles.log 2>&1
     cp gpurun_out/profiles_new/${PFX}_* $out/ 2>/dev/null
