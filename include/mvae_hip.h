@@ -211,6 +211,48 @@ int mvae_convT2d_k4_fwd_stats(const float *x, const float *w, float *part, size_
                               int B, int Cin, int H, int W, int Cout, int stride, int pad,
                               void *ws, size_t ws_bytes, mvae_stream_t stream);
 
+/* Which kernel a 4x4 conv launch takes.  The library picks one of the kernels / template forms below by shape, batch
+ * size and scratch size; this query runs the SAME decision function the launch switches on, launches nothing and
+ * touches no device (like mvae_conv_k4_repack_floats, mvae_convT2d_k4_stats_tiles and mvae_gemm_ws_bytes).
+ *   op        the launch (MVAE_OP_*); B, Cin, H, W, Cout, stride, pad mean exactly what they mean to that launch
+ *   ws_bytes  the scratch that launch would be given (ignored by the launches without one)
+ *   splits    (may be NULL) the number of reduction partials a finish launch sums, 1 where there is none
+ *   returns   a MVAE_ROUTE_* code, or what the launch itself would return for these arguments without launching:
+ *             MVAE_ERR_ARG (bad op / shape, a statistics-only shape that is not covered), MVAE_ERR_WS (scratch too small).
+ * The query ASSUMES 16-BYTE-ALIGNED OPERANDS (with those, which of pre / act / pre_in a call passes does not change the
+ * route); several kernels are only taken for aligned operands, so a launch on a less aligned view may take the
+ * implicit-GEMM launch where the query names another.  MVAE_ROUTE_IGEMM covers the vector- and scalar-weight-load forms
+ * and the tile plans of igemm_kernel: those differ in speed, not in the code path a shape test has to reach. */
+#define MVAE_OP_CONV_FWD        0   /* mvae_conv2d_k4_fwd */
+#define MVAE_OP_CONV_DGRAD      1   /* mvae_conv2d_k4_dgrad */
+#define MVAE_OP_CONV_WGRAD      2   /* mvae_conv2d_k4_wgrad */
+#define MVAE_OP_CONVT_FWD       3   /* mvae_convT2d_k4_fwd */
+#define MVAE_OP_CONVT_FWD_STATS 4   /* mvae_convT2d_k4_fwd_stats */
+#define MVAE_OP_CONVT_DGRAD     5   /* mvae_convT2d_k4_dgrad */
+#define MVAE_OP_CONVT_WGRAD     6   /* mvae_convT2d_k4_wgrad */
+
+#define MVAE_ROUTE_IGEMM            1   /* igemm_kernel on gathered operands (+ split finish for weight gradients) */
+#define MVAE_ROUTE_IGEMM_PAIR       2   /* ... stride-2 dgrad form storing the two column classes of a row as pairs */
+#define MVAE_ROUTE_GEMM2            3   /* gemm2_kernel (forward form; tuning builds only by default) */
+#define MVAE_ROUTE_CONV_PATCH       4   /* conv_patch_kernel (forward form; built in with -DMVAE_CONV_PATCH=1 only) */
+#define MVAE_ROUTE_SMALL_FWD16      5   /* conv_small_fwd_kernel<Cin, 16>: <= 4 input channels, < 1024 blocks of 32 */
+#define MVAE_ROUTE_SMALL_FWD32      6   /* conv_small_fwd_kernel<Cin, 32> */
+#define MVAE_ROUTE_DGRAD_SMALL3D    7   /* convT_small3d_kernel: <= 4 output channels, rows through LDS by DMA */
+#define MVAE_ROUTE_DGRAD_SMALL3     8   /* convT_small3_kernel: ... register-staged */
+#define MVAE_ROUTE_DGRAD_SMALL2     9   /* convT_small2_kernel: ... straight from memory, two quads per thread */
+#define MVAE_ROUTE_DGRAD_SMALL     10   /* convT_small_kernel: the plain form */
+#define MVAE_ROUTE_S1              11   /* convT_s1_kernel<1>: stride 1, dense GEMM + col2im */
+#define MVAE_ROUTE_S1_WIDE         12   /* convT_s1_kernel<2>: 128-column blocks */
+#define MVAE_ROUTE_PATCH8          13   /* convT_patch2_kernel on the 8 x 8 lattice */
+#define MVAE_ROUTE_PATCH7          14   /* ... 7 x 7 */
+#define MVAE_ROUTE_PATCH16         15   /* ... 16 x 16 */
+#define MVAE_ROUTE_PATCH_STATS     16   /* ... 16 x 16, statistics-only records */
+#define MVAE_ROUTE_WGRAD_SMALLCIN  17   /* wgrad_smallcin_kernel<MT, NT> (+ finish) */
+#define MVAE_ROUTE_WGRAD_SMALLCIN2 18   /* wgrad_smallcin2_kernel (+ finish) */
+#define MVAE_ROUTE_WGRAD_PATCH     19   /* wgrad_patch_kernel (+ finish: few <= 16 < normal <= 64 < wide) */
+int mvae_conv_k4_route(int op, int B, int Cin, int H, int W, int Cout, int stride, int pad,
+                       size_t ws_bytes, int *splits /* may be NULL */);
+
 /* ------------------------------------------------------------------------------------
  * K4  BatchNorm2d / BatchNorm1d (training mode, eps 1e-5, momentum 0.1) + fused Swish:
  *     celeba/model.py:80,83,86,118,121,124,149,152,176,179,182; celeba19/model.py:106,109,

@@ -25,6 +25,13 @@ POE_VARIANT = {'A': 0, 'B': 1, 'A-noprior': 0 | POE_NO_PRIOR, 'B-noprior': 1 | P
 MAX_EXPERTS = 32
 STATS_TILE_ELEMS = 512   # MVAE_STATS_TILE_ELEMS
 MAX_TERMS = 40
+# mvae_conv_k4_route: the launches (MVAE_OP_*) and the kernels they take (MVAE_ROUTE_*)
+CONV_OPS = {'conv_fwd': 0, 'conv_dgrad': 1, 'conv_wgrad': 2, 'convT_fwd': 3, 'convT_fwd_stats': 4, 'convT_dgrad': 5,
+            'convT_wgrad': 6}
+CONV_ROUTES = {1: 'igemm', 2: 'igemm_pair', 3: 'gemm2', 4: 'conv_patch', 5: 'small_fwd16', 6: 'small_fwd32',
+               7: 'dgrad_small3d', 8: 'dgrad_small3', 9: 'dgrad_small2', 10: 'dgrad_small', 11: 's1', 12: 's1_wide',
+               13: 'patch8', 14: 'patch7', 15: 'patch16', 16: 'patch_stats', 17: 'wgrad_smallcin',
+               18: 'wgrad_smallcin2', 19: 'wgrad_patch'}
 
 
 class Experts(ctypes.Structure):
@@ -124,6 +131,7 @@ _SIGNATURES = {
     'mvae_conv_k4_repack_batched': (c_int, [ctypes.POINTER(RepackItem), c_int, P]),
     'mvae_convT2d_k4_stats_tiles': (c_size_t, [c_int] * 7),
     'mvae_convT2d_k4_fwd_stats': (c_int, [P, P, P, c_size_t] + [c_int] * 7 + [P, c_size_t, P]),
+    'mvae_conv_k4_route': (c_int, [c_int] * 8 + [c_size_t, ctypes.POINTER(c_int)]),
     'mvae_bn_stats_merge': (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P, c_float, c_float, c_int, P, P]),
     'mvae_linear_wgrad_batched': (c_int, [ctypes.POINTER(WgradItem), c_int, P]),
     'mvae_linear_wgrad_batched_adam': (c_int, [ctypes.POINTER(WgradItem), c_int, ctypes.POINTER(AdamFuse), P]),

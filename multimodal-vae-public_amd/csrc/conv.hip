@@ -959,15 +959,19 @@ inline bool conv_fwd_small_ok(const ConvGeom &g, const float *x, const float *pr
 #ifndef MVAE_SMALL_FWD_CG16
 #define MVAE_SMALL_FWD_CG16 1     // 16-channel groups for launches with < 1024 blocks of 32 (0: A/B builds)
 #endif
+// A thread carries 64 accumulators and walks CIN * 4 dependent trips of six loads: with two blocks per CU (Conv2d(3, 32) at
+// 256 images: 512 blocks) nothing covers a trip's latency -- 22.9 us re-issued hot, 31.5 us in the step, where x comes
+// from HBM.  Half the channels per thread = twice the blocks.
+inline bool conv_fwd_small_half(const ConvGeom &g) {
+    const long total = (long)g.B * g.OH * (g.OW / 2);
+    return MVAE_SMALL_FWD_CG16 && g.Cout % 16 == 0 && ((total + 255) / 256) * ((g.Cout + 31) / 32) < 1024;
+}
+
 inline int conv_fwd_small(const float *x, const float *w, float *pre, float *act, const float *dpre, ConvGeom g,
-                          hipStream_t st) {
+                          bool half, hipStream_t st) {
     const int total = g.B * g.OH * (g.OW / 2);
     const dim3 blk(256);
     dim3 grid((total + 255) / 256, (g.Cout + 31) / 32);
-    // A thread carries 64 accumulators and walks CIN * 4 dependent trips of six loads: with two blocks per CU (Conv2d(3, 32) at
-    // 256 images: 512 blocks) nothing covers a trip's latency -- 22.9 us re-issued hot, 31.5 us in the step, where x comes
-    // from HBM.  Half the channels per thread = twice the blocks.
-    const bool half = MVAE_SMALL_FWD_CG16 && g.Cout % 16 == 0 && (long)grid.x * grid.y < 1024;
     if (half) grid.y = g.Cout / 16;
 #define MVAE_CSF(CV)                                                                                          \
     if (half) hipLaunchKernelGGL((conv_small_fwd_kernel<CV, 16>), grid, blk, 0, st, x, w, pre, act, dpre, g, total); \
@@ -982,12 +986,19 @@ inline int conv_fwd_small(const float *x, const float *w, float *pre, float *act
     return mvae_launch_status();
 }
 
-// ---- conv forward form: y[n][co][oh][ow] = sum_k w[co][k] * im2col(x)[k][(n,oh,ow)] ----
-int conv_fwd_impl(const float *x, const float *w, float *pre, float *act, const float *dpre,
-                  ConvGeom g, hipStream_t st) {
+// ---- which launch a conv-forward-form call takes (conv_fwd_impl switches on it, mvae_conv_k4_route reports it) ----
+struct ConvFwdRoute { int route; Plan pl; ConvPatchPlan pp; G2Plan g2; };
+inline ConvFwdRoute conv_fwd_route(const ConvGeom &g, const float *x, const float *w, const float *pre, const float *act,
+                                   const float *dpre, bool launching) {
+    ConvFwdRoute r;
+    r.pp.kind = 0; r.g2.ok = false;
     const int I = g.Cout, J = g.B * g.OH * g.OW, K = g.Cin * 16;
-    if (conv_fwd_small_ok(g, x, pre, act, dpre) && !MVAE_TUNE(wm)) return conv_fwd_small(x, w, pre, act, dpre, g, st);
-    Plan pl = make_plan(I, J, K, false);
+    if (conv_fwd_small_ok(g, x, pre, act, dpre) && !MVAE_TUNE(wm)) {
+        r.route = conv_fwd_small_half(g) ? MVAE_ROUTE_SMALL_FWD16 : MVAE_ROUTE_SMALL_FWD32;
+        return r;
+    }
+    Plan &pl = r.pl;
+    pl = make_plan(I, J, K, false);
     // >= 128 output channels and enough columns for >= 384 blocks of 128 x 64: two accumulators per wave share
     // every gathered fragment (dec2 / dec1 dgrad at 512 images: 91 -> 99 and 77 -> 80 TFLOP/s; at 256 images the
     // grid would be one block per CU and 64 x 64 tiles win)
@@ -996,35 +1007,53 @@ int conv_fwd_impl(const float *x, const float *w, float *pre, float *act, const 
         pl.wm = 2;
     if (K <= MVAE_MULTI_MAXK) pl.items = MVAE_MULTI_ITEMS;      // short reductions: pipeline across consecutive tiles
     pl.xcd = MVAE_CONV_XCD ? 3 : 0;                             // the bands of one column tile on one XCD (igemm_kernel)
-    EpNCHW e;
-    e.out = pre; e.act = act; e.dpre = dpre;
-    e.C = g.Cout; e.HW = g.OH * g.OW; e.Wfull = g.OW; e.H2 = g.OH; e.W2 = g.OW;
-    e.sy = 1; e.py = 0; e.px = 0; e.J = J; e.off = 0;
-    e.lg_hw2 = g.lg_ohw; e.lg_w2 = g.lg_ow;
     if (MVAE_CONV_PATCH && aligned16(w) && aligned16(x) && MVAE_EP_BUFFER && !MVAE_TUNE(wm)) {
         // the input as an LDS patch, the weights as they lie in memory (conv_patch.h)
-        const ConvPatchPlan pp = conv_patch_plan(g.B, g.Cin, g.H, g.W, g.Cout, g.OH, g.OW, g.stride, g.pad);
-        if (pp.kind == 1 || pp.kind == 4) return launch_conv_patch<260>(pp, x, w, e, st);
-        if (pp.kind == 2) return launch_conv_patch<324>(pp, x, w, e, st);
-        if (pp.kind == 3) return launch_conv_patch<592>(pp, x, w, e, st);
+        r.pp = conv_patch_plan(g.B, g.Cin, g.H, g.W, g.Cout, g.OH, g.OW, g.stride, g.pad);
+        if (r.pp.kind >= 1 && r.pp.kind <= 4) { r.route = MVAE_ROUTE_CONV_PATCH; return r; }
     }
-    auto mp = [&](auto &p) { p.src = w; p.ld = K; p.R = I; p.Klen = K; };
-    auto mq = [&](auto &q) { q.x = x; q.g = g; q.Mtot = J; };
     if (aligned16(w) && (size_t)g.Cin * g.H * g.W * 4 * (256 / (g.OH * g.OW) + 2) < ((size_t)1 << 31)) {
         void *g2ws = nullptr; size_t g2ws_bytes = 0;
 #ifdef MVAE_TUNING
-        {   // experiments only: the forward entry points carry no scratch argument (the persistent modes' slabs need one)
+        if (launching) {   // experiments only: the forward entry points carry no scratch argument (the persistent modes' slabs need one)
             static void *tune_ws = nullptr;
             if (!tune_ws && getenv("MVAE_G2_FORCE")) (void)hipMalloc(&tune_ws, (size_t)256 << 20);
             g2ws = tune_ws; g2ws_bytes = tune_ws ? (size_t)256 << 20 : 0;
         }
 #endif
-        G2Plan g2 = g2_plan_for(I, J, K, 1, false, g2ws, g2ws_bytes, G2_CONV_FWD);
-        if (g2.ok) return launch_gemm2<G2RowsK, G2Im2col, EpNCHW, false>(g2, mp, mq, e, st);
+        (void)launching;
+        r.g2 = g2_plan_for(I, J, K, 1, false, g2ws, g2ws_bytes, G2_CONV_FWD);
+        if (r.g2.ok) { r.route = MVAE_ROUTE_GEMM2; return r; }
     }
-    if (aligned16(w))
-        return launch_igemm<LdRowsKC, LdIm2col, EpNCHW, false>(pl, mp, mq, e, I, J, K, make_sink(nullptr, I, J, false), st);
-    return launch_igemm<LdRowsKSC, LdIm2col, EpNCHW, false>(pl, mp, mq, e, I, J, K, make_sink(nullptr, I, J, false), st);
+    r.route = MVAE_ROUTE_IGEMM;
+    return r;
+}
+
+// ---- conv forward form: y[n][co][oh][ow] = sum_k w[co][k] * im2col(x)[k][(n,oh,ow)] ----
+int conv_fwd_impl(const float *x, const float *w, float *pre, float *act, const float *dpre,
+                  ConvGeom g, hipStream_t st) {
+    const int I = g.Cout, J = g.B * g.OH * g.OW, K = g.Cin * 16;
+    const ConvFwdRoute r = conv_fwd_route(g, x, w, pre, act, dpre, true);
+    EpNCHW e;
+    e.out = pre; e.act = act; e.dpre = dpre;
+    e.C = g.Cout; e.HW = g.OH * g.OW; e.Wfull = g.OW; e.H2 = g.OH; e.W2 = g.OW;
+    e.sy = 1; e.py = 0; e.px = 0; e.J = J; e.off = 0;
+    e.lg_hw2 = g.lg_ohw; e.lg_w2 = g.lg_ow;
+    auto mp = [&](auto &p) { p.src = w; p.ld = K; p.R = I; p.Klen = K; };
+    auto mq = [&](auto &q) { q.x = x; q.g = g; q.Mtot = J; };
+    switch (r.route) {
+        case MVAE_ROUTE_SMALL_FWD16: return conv_fwd_small(x, w, pre, act, dpre, g, true, st);
+        case MVAE_ROUTE_SMALL_FWD32: return conv_fwd_small(x, w, pre, act, dpre, g, false, st);
+        case MVAE_ROUTE_CONV_PATCH:
+            if (r.pp.kind == 2) return launch_conv_patch<324>(r.pp, x, w, e, st);
+            if (r.pp.kind == 3) return launch_conv_patch<592>(r.pp, x, w, e, st);
+            return launch_conv_patch<260>(r.pp, x, w, e, st);                    // kinds 1 and 4
+        case MVAE_ROUTE_GEMM2: return launch_gemm2<G2RowsK, G2Im2col, EpNCHW, false>(r.g2, mp, mq, e, st);
+        default: break;
+    }
+    if (aligned16(w))       // (not a route: the same kernel with vector / scalar weight loads)
+        return launch_igemm<LdRowsKC, LdIm2col, EpNCHW, false>(r.pl, mp, mq, e, I, J, K, make_sink(nullptr, I, J, false), st);
+    return launch_igemm<LdRowsKSC, LdIm2col, EpNCHW, false>(r.pl, mp, mq, e, I, J, K, make_sink(nullptr, I, J, false), st);
 }
 
 // ---- direct transposed conv for <= 4 OUTPUT channels (ConvTranspose2d(32,3) / (64,1), stride 2,
@@ -1471,51 +1500,68 @@ inline bool conv_dgrad_small_ok(const ConvGeom &g) {
            (size_t)g.Cout * g.Cin * 16 * sizeof(float) <= 48 * 1024;
 }
 
-inline int conv_dgrad_small(const float *dy, const float *w, float *dx, float *act, const float *dpre,
+// the DMA form of the LDS-staged kernel: pieces of 64 floats, at most 12 per channel image (three per wave), four channels
+// per stage
+inline bool conv_small3_dma_plan(const ConvGeom &g, const Small3Geo &sg, int &qpw, size_t &ldsd) {
+    const int nq = (sg.ch_stride + 63) / 64;
+    qpw = (nq + 3) / 4;
+    ldsd = ((size_t)3 * 4 * nq * 64 + 256) * sizeof(float);
+    return MVAE_SMALL3_DMA && g.Cout % 4 == 0 && qpw >= 2 && qpw <= 3 && ldsd <= 48 * 1024;
+}
+
+// which of the direct <= 4-channel kernels a launch takes (conv_dgrad_small switches on it)
+inline int conv_dgrad_small_route(const ConvGeom &g, const float *dy, const float *dx, const float *act, const float *dpre) {
+    Small3Geo sg; int depth; size_t lds3;
+    if (conv_small3_plan(g, sg, depth, lds3) && aligned16(dx ? dx : act) && (!dx || !act || aligned16(act)) &&
+        (!dpre || aligned16(dpre)) && (2 * g.OW) % 4 == 0) {
+        int qpw; size_t ldsd;
+        return conv_small3_dma_plan(g, sg, qpw, ldsd) ? MVAE_ROUTE_DGRAD_SMALL3D : MVAE_ROUTE_DGRAD_SMALL3;
+    }
+    if (MVAE_CONVT_SMALL2 && g.OW % 2 == 0 && aligned16(dx ? dx : act) && (!dx || !act || aligned16(act)) && (!dpre || aligned16(dpre)) &&
+        aligned8(dy))
+        return MVAE_ROUTE_DGRAD_SMALL2;
+    return MVAE_ROUTE_DGRAD_SMALL;
+}
+
+inline int conv_dgrad_small(int route, const float *dy, const float *w, float *dx, float *act, const float *dpre,
                             ConvGeom g, hipStream_t st) {
     const int total = g.B * g.OH * g.OW;
     const size_t lds = (size_t)g.Cout * g.Cin * 16 * sizeof(float);
     const dim3 grid((total + 255) / 256), blk(256);
-    {
+    if (route == MVAE_ROUTE_DGRAD_SMALL3D || route == MVAE_ROUTE_DGRAD_SMALL3) {
         Small3Geo sg; int depth; size_t lds3;
-        if (conv_small3_plan(g, sg, depth, lds3) && aligned16(dx ? dx : act) && (!dx || !act || aligned16(act)) &&
-            (!dpre || aligned16(dpre)) && (2 * g.OW) % 4 == 0) {
-            const dim3 grid3((g.B + sg.NI - 1) / sg.NI, sg.bands);
-            {
-                // the DMA form: pieces of 64 floats, at most 12 per channel image (three per wave), four channels per stage
-                const int nq = (sg.ch_stride + 63) / 64, qpw = (nq + 3) / 4;
-                const size_t ldsd = ((size_t)3 * 4 * nq * 64 + 256) * sizeof(float);
-                if (MVAE_SMALL3_DMA && g.Cout % 4 == 0 && qpw >= 2 && qpw <= 3 && ldsd <= 48 * 1024) {
+        (void)conv_small3_plan(g, sg, depth, lds3);
+        const dim3 grid3((g.B + sg.NI - 1) / sg.NI, sg.bands);
+        if (route == MVAE_ROUTE_DGRAD_SMALL3D) {
+            int qpw; size_t ldsd;
+            (void)conv_small3_dma_plan(g, sg, qpw, ldsd);
 #define MVAE_S3DMA(CV)                                                                                                   \
-                    if (qpw == 2) hipLaunchKernelGGL((convT_small3d_kernel<CV, 4, 2>), grid3, blk, ldsd, st, dy, w, dx, act, dpre, g, sg); \
-                    else hipLaunchKernelGGL((convT_small3d_kernel<CV, 4, 3>), grid3, blk, ldsd, st, dy, w, dx, act, dpre, g, sg);
-                    switch (g.Cin) {
-                        case 1: MVAE_S3DMA(1) break;
-                        case 2: MVAE_S3DMA(2) break;
-                        case 3: MVAE_S3DMA(3) break;
-                        default: MVAE_S3DMA(4) break;
-                    }
-#undef MVAE_S3DMA
-                    return mvae_launch_status();
-                }
-            }
-#define MVAE_S3(CV, DV) hipLaunchKernelGGL((convT_small3_kernel<CV, DV>), grid3, blk, lds3, st, dy, w, dx, act, dpre, g, sg)
-#define MVAE_S3D(CV)                                                                                     \
-            if (depth == 8) MVAE_S3(CV, 8); else if (depth == 4) MVAE_S3(CV, 4);                         \
-            else if (depth == 2) MVAE_S3(CV, 2); else MVAE_S3(CV, 1);
+            if (qpw == 2) hipLaunchKernelGGL((convT_small3d_kernel<CV, 4, 2>), grid3, blk, ldsd, st, dy, w, dx, act, dpre, g, sg); \
+            else hipLaunchKernelGGL((convT_small3d_kernel<CV, 4, 3>), grid3, blk, ldsd, st, dy, w, dx, act, dpre, g, sg);
             switch (g.Cin) {
-                case 1: MVAE_S3D(1) break;
-                case 2: MVAE_S3D(2) break;
-                case 3: MVAE_S3D(3) break;
-                default: MVAE_S3D(4) break;
+                case 1: MVAE_S3DMA(1) break;
+                case 2: MVAE_S3DMA(2) break;
+                case 3: MVAE_S3DMA(3) break;
+                default: MVAE_S3DMA(4) break;
             }
-#undef MVAE_S3D
-#undef MVAE_S3
+#undef MVAE_S3DMA
             return mvae_launch_status();
         }
+#define MVAE_S3(CV, DV) hipLaunchKernelGGL((convT_small3_kernel<CV, DV>), grid3, blk, lds3, st, dy, w, dx, act, dpre, g, sg)
+#define MVAE_S3D(CV)                                                                                     \
+        if (depth == 8) MVAE_S3(CV, 8); else if (depth == 4) MVAE_S3(CV, 4);                             \
+        else if (depth == 2) MVAE_S3(CV, 2); else MVAE_S3(CV, 1);
+        switch (g.Cin) {
+            case 1: MVAE_S3D(1) break;
+            case 2: MVAE_S3D(2) break;
+            case 3: MVAE_S3D(3) break;
+            default: MVAE_S3D(4) break;
+        }
+#undef MVAE_S3D
+#undef MVAE_S3
+        return mvae_launch_status();
     }
-    if (MVAE_CONVT_SMALL2 && g.OW % 2 == 0 && aligned16(dx ? dx : act) && (!dx || !act || aligned16(act)) && (!dpre || aligned16(dpre)) &&
-        aligned8(dy)) {
+    if (route == MVAE_ROUTE_DGRAD_SMALL2) {
         const int total2 = total / 2;
         const dim3 grid2((total2 + 255) / 256);
         // channels fetched per trip: MVAE_SMALL2_DEPTH, as far as it divides the channel count (8 only with one output
@@ -1930,14 +1976,27 @@ inline bool conv_dgrad_s1_ok(const ConvGeom &g, const float *w) {
            (size_t)128 * g.Cout * g.OH * g.OW * 4 < (1ull << 31);
 }
 
-inline int conv_dgrad_s1(const float *dy, const float *w, float *dx, float *act, const float *dpre, ConvGeom g,
-                         hipStream_t st) {
+inline dim3 conv_dgrad_s1_grid(const ConvGeom &g) {
     const int NI = S1_ROWS / (g.OH * g.OW);         // whole images per block
     dim3 grid(g.Cin / 4, (g.B + NI - 1) / NI);
     if (MVAE_S1_XCD) grid.y = (grid.y + 7) / 8 * 8;   // XCD-local image groups (see the kernel)
+    return grid;
+}
+// 128-column blocks (three per CU) where the launch still has MVAE_S1_WIDE_MIN of them: the 4608-image passes of celeba19
+inline bool conv_dgrad_s1_wide(const ConvGeom &g) {
 #if MVAE_S1_DMA
-    // 128-column blocks (three per CU) where the launch still has MVAE_S1_WIDE_MIN of them: the 4608-image passes of celeba19
-    if (MVAE_S1_WIDE_MIN > 0 && g.Cin % 8 == 0 && (long)(g.Cin / 8) * grid.y >= MVAE_S1_WIDE_MIN) {
+    return MVAE_S1_WIDE_MIN > 0 && g.Cin % 8 == 0 && (long)(g.Cin / 8) * conv_dgrad_s1_grid(g).y >= MVAE_S1_WIDE_MIN;
+#else
+    return false;
+#endif
+}
+
+inline int conv_dgrad_s1(bool wide, const float *dy, const float *w, float *dx, float *act, const float *dpre, ConvGeom g,
+                         hipStream_t st) {
+    const int NI = S1_ROWS / (g.OH * g.OW);
+    dim3 grid = conv_dgrad_s1_grid(g);
+#if MVAE_S1_DMA
+    if (wide) {
         grid.x = g.Cin / 8;
         hipLaunchKernelGGL(convT_s1_kernel<2>, grid, dim3(256), 0, st, dy, w, dx, act, dpre, g, NI);
         return mvae_launch_status();
@@ -1949,34 +2008,6 @@ inline int conv_dgrad_s1(const float *dy, const float *w, float *dx, float *act,
 
 inline size_t dgrad_ws_floats(const ConvGeom &g) { return (size_t)g.Cout * g.Cin * 16; }
 
-// ---- conv dgrad form: dx[n][ci][ih][iw] = sum_(co,kh,kw) w[co][ci][kh][kw] * dy[n][co][oh][ow],
-//      one launch per output parity class (4 for stride 2, 1 for stride 1) on repacked weights ----
-int conv_dgrad_impl(const float *dy, const float *w, float *dx, float *act, const float *dpre,
-                    ConvGeom g, void *ws, size_t ws_bytes, hipStream_t st) {
-    const int s = g.stride, tlog = (s == 2) ? 1 : 2;
-    const int H2 = g.H / s, W2 = g.W / s;
-    const int I = g.Cin, J = g.B * H2 * W2, K = g.Cout << (2 * tlog);
-    // w == NULL: `ws` already holds the repacked weights (mvae_conv_k4_repack_batched) -- only valid for launches
-    // that read them (mvae_conv_k4_repack_floats != 0)
-    if (conv_dgrad_small_ok(g) && !MVAE_TUNE(wm)) return w ? conv_dgrad_small(dy, w, dx, act, dpre, g, st) : MVAE_ERR_ARG;
-    if (conv_dgrad_s1_ok(g, w) && !MVAE_TUNE(wm)) return w ? conv_dgrad_s1(dy, w, dx, act, dpre, g, st) : MVAE_ERR_ARG;
-    if (!ws || ws_bytes < dgrad_ws_floats(g) * sizeof(float)) return MVAE_ERR_WS;
-    float *wr = (float *)ws;
-    if (w) {
-        const int total = s * s * K * g.Cin;
-        int blocks = (total + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(repack_dgrad_weights_kernel, dim3(blocks), dim3(256), 0, st, w, wr, g.Cout, g.Cin, s, g.pad);
-    }
-    Plan pl = make_plan(I, J, K, false, PLAN_FWD, s * s);
-    if (K <= MVAE_MULTI_MAXK) pl.items = MVAE_MULTI_ITEMS;      // short reductions: pipeline across consecutive tiles / classes
-    pl.xcd = MVAE_CONV_XCD ? 3 : 0;
-    const bool vec = (g.Cin % 4 == 0) && aligned16(wr);
-    EpNCHW e;
-    e.out = dx; e.act = act; e.dpre = dpre;
-    e.C = g.Cin; e.HW = g.H * g.W; e.Wfull = g.W; e.H2 = H2; e.W2 = W2;
-    e.sy = s; e.py = 0; e.px = 0; e.J = J; e.off = 0;
-    e.lg_hw2 = g.lg_hw2; e.lg_w2 = g.lg_w2;
 #ifndef MVAE_PAIR_STORE
 #define MVAE_PAIR_STORE 1
 #endif
@@ -1986,9 +2017,83 @@ int conv_dgrad_impl(const float *dy, const float *w, float *dx, float *act, cons
 #ifndef MVAE_PAIR_MINBLOCKS
 #define MVAE_PAIR_MINBLOCKS 2048
 #endif
+
+// ---- which launch a dgrad-form call takes (conv_dgrad_impl switches on it, mvae_conv_k4_route reports it).  `wr`: the
+//      repacked weight copy the launch reads (the caller's scratch); `w` only for the alignment gate of the stride-1 kernel ----
+struct ConvDgradRoute { int route; Plan pl; PatchPlan pp; bool vec; int pair; };
+inline ConvDgradRoute conv_dgrad_route(const ConvGeom &g, const float *dy, const float *w, const float *wr, const float *dx,
+                                       const float *act, const float *dpre) {
+    ConvDgradRoute r;
+    r.pp.kind = 0; r.vec = false; r.pair = 0;
+    const int s = g.stride, tlog = (s == 2) ? 1 : 2;
+    const int H2 = g.H / s, W2 = g.W / s;
+    const int I = g.Cin, J = g.B * H2 * W2, K = g.Cout << (2 * tlog);
+    if (conv_dgrad_small_ok(g) && !MVAE_TUNE(wm)) { r.route = conv_dgrad_small_route(g, dy, dx, act, dpre); return r; }
+    if (conv_dgrad_s1_ok(g, w) && !MVAE_TUNE(wm)) { r.route = conv_dgrad_s1_wide(g) ? MVAE_ROUTE_S1_WIDE : MVAE_ROUTE_S1; return r; }
+    Plan &pl = r.pl;
+    pl = make_plan(I, J, K, false, PLAN_FWD, s * s);
+    if (K <= MVAE_MULTI_MAXK) pl.items = MVAE_MULTI_ITEMS;      // short reductions: pipeline across consecutive tiles / classes
+    pl.xcd = MVAE_CONV_XCD ? 3 : 0;
+    r.vec = (g.Cin % 4 == 0) && aligned16(wr);
     // pair stores (gemm_core.h EpNCHW::PAIR): class-minor item order puts (py, 0), (py, 1) back to back in a block
-    e.pair = (MVAE_PAIR_STORE && s == 2 && MVAE_CLS_MINOR && g.W % 2 == 0 && (!dx || aligned8(dx)) && (!act || aligned8(act)) &&
+    r.pair = (MVAE_PAIR_STORE && s == 2 && MVAE_CLS_MINOR && g.W % 2 == 0 && (!dx || aligned8(dx)) && (!act || aligned8(act)) &&
               (!dpre || aligned8(dpre))) ? 1 : 0;
+    r.route = MVAE_ROUTE_IGEMM;
+    if (r.vec && s == 2 && r.pair && MVAE_EP_BUFFER && !MVAE_TUNE(wm) && aligned16(dy)) {
+        // one LDS input patch for the four parity classes (convt_patch.h): the 64- and 32-row layers on 7 x 7 / 8 x 8 / 16 x 16 maps
+        r.pp = convt_patch_plan(g.B, g.Cout, g.Cin, g.OH, g.OW, false);
+        if (r.pp.kind == 1) { r.route = MVAE_ROUTE_PATCH8; return r; }
+        if (r.pp.kind == 2) { r.route = MVAE_ROUTE_PATCH7; return r; }
+        if (r.pp.kind == 3) { r.route = MVAE_ROUTE_PATCH16; return r; }
+    }
+    if (r.vec) {
+        // pair stores want the two px classes of a tile in ONE block.  Short reductions (K <= 256) run multi-item
+        // blocks anyway; for K = 512 (the 64-channel layers) two items per block pay only when the launch still
+        // has >= 8 blocks per CU afterwards (measured: FashionMNIST's 2048-row ConvTranspose2d(128, 64) -2.9 % of
+        // the step, CelebA's 512-row one +0.9 %: profiles/r03_pair_store_ab.txt)
+        const long pair_blocks = cdiv(J, pl.wgn == 4 ? 128 : 64) * 4 / 2;
+        const bool pair_long = K > MVAE_MULTI_MAXK && K <= MVAE_PAIR_MAXK && pair_blocks >= MVAE_PAIR_MINBLOCKS;
+        if (s == 2 && r.pair && pl.wm * pl.wn == 1 && pl.kw == 1 && (K <= MVAE_MULTI_MAXK || pair_long)) {
+            if (pair_long) pl.items = 2;
+            r.route = MVAE_ROUTE_IGEMM_PAIR;
+        }
+    }
+    return r;
+}
+
+// ---- conv dgrad form: dx[n][ci][ih][iw] = sum_(co,kh,kw) w[co][ci][kh][kw] * dy[n][co][oh][ow],
+//      one launch per output parity class (4 for stride 2, 1 for stride 1) on repacked weights ----
+int conv_dgrad_impl(const float *dy, const float *w, float *dx, float *act, const float *dpre,
+                    ConvGeom g, void *ws, size_t ws_bytes, hipStream_t st) {
+    const int s = g.stride, tlog = (s == 2) ? 1 : 2;
+    const int H2 = g.H / s, W2 = g.W / s;
+    const int I = g.Cin, J = g.B * H2 * W2, K = g.Cout << (2 * tlog);
+    float *wr = (float *)ws;
+    const ConvDgradRoute r = conv_dgrad_route(g, dy, w, wr, dx, act, dpre);
+    // w == NULL: `ws` already holds the repacked weights (mvae_conv_k4_repack_batched) -- only valid for launches
+    // that read them (mvae_conv_k4_repack_floats != 0)
+    switch (r.route) {
+        case MVAE_ROUTE_DGRAD_SMALL3D: case MVAE_ROUTE_DGRAD_SMALL3: case MVAE_ROUTE_DGRAD_SMALL2: case MVAE_ROUTE_DGRAD_SMALL:
+            return w ? conv_dgrad_small(r.route, dy, w, dx, act, dpre, g, st) : MVAE_ERR_ARG;
+        case MVAE_ROUTE_S1: case MVAE_ROUTE_S1_WIDE:
+            return w ? conv_dgrad_s1(r.route == MVAE_ROUTE_S1_WIDE, dy, w, dx, act, dpre, g, st) : MVAE_ERR_ARG;
+        default: break;
+    }
+    if (!ws || ws_bytes < dgrad_ws_floats(g) * sizeof(float)) return MVAE_ERR_WS;
+    if (w) {
+        const int total = s * s * K * g.Cin;
+        int blocks = (total + 255) / 256;
+        if (blocks > 2048) blocks = 2048;
+        hipLaunchKernelGGL(repack_dgrad_weights_kernel, dim3(blocks), dim3(256), 0, st, w, wr, g.Cout, g.Cin, s, g.pad);
+    }
+    EpNCHW e;
+    e.out = dx; e.act = act; e.dpre = dpre;
+    e.C = g.Cin; e.HW = g.H * g.W; e.Wfull = g.W; e.H2 = H2; e.W2 = W2;
+    e.sy = s; e.py = 0; e.px = 0; e.J = J; e.off = 0;
+    e.lg_hw2 = g.lg_hw2; e.lg_w2 = g.lg_w2;
+    e.pair = r.pair;
+    EpNCHWPair ep;
+    static_cast<EpNCHW &>(ep) = e;
     auto mp = [&](auto &p) {
         p.src = wr; p.ld = g.Cin; p.R = g.Cin; p.Klen = K; p.cls_stride = (size_t)K * g.Cin;
     };
@@ -1996,35 +2101,20 @@ int conv_dgrad_impl(const float *dy, const float *w, float *dx, float *act, cons
     SplitSink sink = make_sink(nullptr, I, J, false);
     sink.ncls = s * s;      // all parity classes in ONE launch: s*s times the blocks
     sink.cls_minor = MVAE_CLS_MINOR;
-    if (vec && s == 2 && e.pair && MVAE_EP_BUFFER && !MVAE_TUNE(wm) && aligned16(dy)) {
-        // one LDS input patch for the four parity classes (convt_patch.h): the 64- and 32-row layers on 7 x 7 / 8 x 8 / 16 x 16 maps
-        const PatchPlan pp = convt_patch_plan(g.B, g.Cout, g.Cin, g.OH, g.OW, false);
-        if (pp.kind) {
-            EpNCHWPair ep;
-            static_cast<EpNCHW &>(ep) = e;
-            if (pp.kind == 1) return launch_convt_patch2<EpNCHWPair, 1, 68, true, MVAE_PATCH_STAGE8 ? 8 : 0, 8>(pp, dy, wr, ep, st);
-            if (pp.kind == 2) return launch_convt_patch2<EpNCHWPair, 1, 148, false, MVAE_PATCH_STAGE7 ? 7 : 0, 11>(pp, dy, wr, ep, st);
-            if (pp.kind == 3) return launch_convt_patch2<EpNCHWPair, 1, 100, true>(pp, dy, wr, ep, st);
-        }
+    switch (r.route) {
+        case MVAE_ROUTE_PATCH8: return launch_convt_patch2<EpNCHWPair, 1, 68, true, MVAE_PATCH_STAGE8 ? 8 : 0, 8>(r.pp, dy, wr, ep, st);
+        case MVAE_ROUTE_PATCH7: return launch_convt_patch2<EpNCHWPair, 1, 148, false, MVAE_PATCH_STAGE7 ? 7 : 0, 11>(r.pp, dy, wr, ep, st);
+        case MVAE_ROUTE_PATCH16: return launch_convt_patch2<EpNCHWPair, 1, 100, true>(r.pp, dy, wr, ep, st);
+        case MVAE_ROUTE_IGEMM_PAIR: return launch_igemm<LdRowsMNC, LdDgradDyS2, EpNCHWPair, false>(r.pl, mp, mq, ep, I, J, K, sink, st);
+        default: break;
     }
-    if (vec) {
-        // pair stores want the two px classes of a tile in ONE block.  Short reductions (K <= 256) run multi-item
-        // blocks anyway; for K = 512 (the 64-channel layers) two items per block pay only when the launch still
-        // has >= 8 blocks per CU afterwards (measured: FashionMNIST's 2048-row ConvTranspose2d(128, 64) -2.9 % of
-        // the step, CelebA's 512-row one +0.9 %: profiles/r03_pair_store_ab.txt)
-        const long pair_blocks = cdiv(J, pl.wgn == 4 ? 128 : 64) * 4 / 2;
-        const bool pair_long = K > MVAE_MULTI_MAXK && K <= MVAE_PAIR_MAXK && pair_blocks >= MVAE_PAIR_MINBLOCKS;
-        if (s == 2 && e.pair && pl.wm * pl.wn == 1 && pl.kw == 1 && (K <= MVAE_MULTI_MAXK || pair_long)) {
-            if (pair_long) pl.items = 2;
-            EpNCHWPair ep;
-            static_cast<EpNCHW &>(ep) = e;
-            return launch_igemm<LdRowsMNC, LdDgradDyS2, EpNCHWPair, false>(pl, mp, mq, ep, I, J, K, sink, st);
-        }
-        if (s == 2) return launch_igemm<LdRowsMNC, LdDgradDyS2, EpNCHW, false>(pl, mp, mq, e, I, J, K, sink, st);
-        return launch_igemm<LdRowsMNC, LdDgradDyS1, EpNCHW, false>(pl, mp, mq, e, I, J, K, sink, st);
+    // (not routes: the same kernel with vector / scalar weight loads, stride 2 / 1 tap sets)
+    if (r.vec) {
+        if (s == 2) return launch_igemm<LdRowsMNC, LdDgradDyS2, EpNCHW, false>(r.pl, mp, mq, e, I, J, K, sink, st);
+        return launch_igemm<LdRowsMNC, LdDgradDyS1, EpNCHW, false>(r.pl, mp, mq, e, I, J, K, sink, st);
     }
-    if (s == 2) return launch_igemm<LdRowsMNSC, LdDgradDyS2, EpNCHW, false>(pl, mp, mq, e, I, J, K, sink, st);
-    return launch_igemm<LdRowsMNSC, LdDgradDyS1, EpNCHW, false>(pl, mp, mq, e, I, J, K, sink, st);
+    if (s == 2) return launch_igemm<LdRowsMNSC, LdDgradDyS2, EpNCHW, false>(r.pl, mp, mq, e, I, J, K, sink, st);
+    return launch_igemm<LdRowsMNSC, LdDgradDyS1, EpNCHW, false>(r.pl, mp, mq, e, I, J, K, sink, st);
 }
 
 // ---- statistics-only form of the stride-2 dgrad-form launch (EpStats, gemm_core.h): the transposed conv in front of a
@@ -2042,6 +2132,26 @@ inline long conv_dgrad_stats_tiles(const ConvGeom &g) {
     return J / STATS_TILE;
 }
 
+// which launch the statistics-only call takes, or MVAE_ERR_ARG where it is not covered
+struct ConvStatsRoute { int route; Plan pl; PatchPlan pp; };
+inline ConvStatsRoute conv_dgrad_stats_route(const ConvGeom &g, const float *dy, const float *wr) {
+    ConvStatsRoute r;
+    r.pp.kind = 0; r.route = MVAE_ERR_ARG;
+    const int s = g.stride;
+    if (!conv_dgrad_stats_tiles(g) || !aligned16(wr)) return r;
+    const int I = g.Cin, J = g.B * (g.H / s) * (g.W / s), K = g.Cout << 2;
+    if (!MVAE_TUNE(wm) && aligned16(dy)) {
+        r.pp = convt_patch_plan(g.B, g.Cout, g.Cin, g.OH, g.OW, true);
+        if (r.pp.kind == 4) { r.route = MVAE_ROUTE_PATCH_STATS; return r; }     // one record per 128-column tile, as below
+    }
+    Plan &pl = r.pl;
+    pl = make_plan(I, J, K, false, PLAN_FWD, s * s);
+    if (!(pl.wgn == 4 && pl.wm == 1 && pl.wn == 1 && pl.kw == 1 && pl.splits == 1)) return r;   // the 32-row layout
+    pl.items = s * s; pl.force_items = 1;               // a block = the four classes of one column tile
+    r.route = MVAE_ROUTE_IGEMM;
+    return r;
+}
+
 int conv_dgrad_stats_impl(const float *dy, const float *w, float *part, ConvGeom g, void *ws, size_t ws_bytes,
                           hipStream_t st) {
     const int s = g.stride;
@@ -2050,32 +2160,23 @@ int conv_dgrad_stats_impl(const float *dy, const float *w, float *part, ConvGeom
     if (!conv_dgrad_stats_tiles(g)) return MVAE_ERR_ARG;
     if (!ws || ws_bytes < dgrad_ws_floats(g) * sizeof(float)) return MVAE_ERR_WS;
     float *wr = (float *)ws;
-    if (!aligned16(wr)) return MVAE_ERR_ARG;
+    const ConvStatsRoute r = conv_dgrad_stats_route(g, dy, wr);
+    if (r.route < 0) return r.route;                    // before anything is launched
     if (w) {
         const int total = s * s * K * g.Cin;
         int blocks = (total + 255) / 256;
         if (blocks > 2048) blocks = 2048;
         hipLaunchKernelGGL(repack_dgrad_weights_kernel, dim3(blocks), dim3(256), 0, st, w, wr, g.Cout, g.Cin, s, g.pad);
     }
-    if (!MVAE_TUNE(wm) && aligned16(dy)) {
-        const PatchPlan pp = convt_patch_plan(g.B, g.Cout, g.Cin, g.OH, g.OW, true);
-        if (pp.kind == 4) {                                 // one record per 128-column tile, as below
-            EpStats es;
-            es.part = part; es.C = g.Cin; es.J = J;
-            return launch_convt_patch2<EpStats, 2, 100, true>(pp, dy, wr, es, st);
-        }
-    }
-    Plan pl = make_plan(I, J, K, false, PLAN_FWD, s * s);
-    if (!(pl.wgn == 4 && pl.wm == 1 && pl.wn == 1 && pl.kw == 1 && pl.splits == 1)) return MVAE_ERR_ARG;   // the 32-row layout
-    pl.items = s * s; pl.force_items = 1;               // a block = the four classes of one column tile
     EpStats e;
     e.part = part; e.C = g.Cin; e.J = J;
+    if (r.route == MVAE_ROUTE_PATCH_STATS) return launch_convt_patch2<EpStats, 2, 100, true>(r.pp, dy, wr, e, st);
     auto mp = [&](auto &p) { p.src = wr; p.ld = g.Cin; p.R = g.Cin; p.Klen = K; p.cls_stride = (size_t)K * g.Cin; };
     auto mq = [&](auto &q) { q.dy = dy; q.g = g; q.Mtot = J; q.H2 = H2; q.W2 = W2; };
     SplitSink sink = make_sink(nullptr, I, J, false);
     sink.ncls = s * s;
     sink.cls_minor = 1;
-    return launch_igemm<LdRowsMNC, LdDgradDyS2, EpStats, false>(pl, mp, mq, e, I, J, K, sink, st);
+    return launch_igemm<LdRowsMNC, LdDgradDyS2, EpStats, false>(r.pl, mp, mq, e, I, J, K, sink, st);
 }
 
 // ---- weight gradient of the <= 4-input-channel convs (Conv2d(3,32) / ConvTranspose2d(32,3) of CelebA,
@@ -2408,6 +2509,57 @@ inline int wgrad_smallcin_blocks(const ConvGeom &g) {
     return blocks > MVAE_SC_BLOCKS ? MVAE_SC_BLOCKS : blocks;
 }
 
+// the LDS-DMA kernel's launch geometry; false: no instantiation for this layer (the register-staged kernel runs it)
+struct Sc2Geo { int xw, p; size_t lds; };
+inline bool wgrad_smallcin2_plan(const ConvGeom &g, Sc2Geo &q) {
+    if (!MVAE_SC2) return false;
+    const int I = g.Cout, J = g.Cin * 16;
+    const int mt = I / 32, nt = (J + 31) / 32;
+    q.xw = g.W + 8;
+    if (((q.xw / 4) & 1) == 0) q.xw += 4;                       // pitch = 4 x odd: the tap columns of a tile hit 32 banks
+    q.p = g.OW <= 16 ? 16 : 32;
+    const size_t stage_f = (size_t)I * q.p + (size_t)g.Cin * 4 * q.xw;
+    const size_t red_f = (size_t)(SC2_WAVES - 1) * mt * nt * 1024;
+    q.lds = (size_t)SC2_WAVES * MVAE_SC2_STAGES * stage_f;
+    if (red_f > q.lds) q.lds = red_f;
+    q.lds *= sizeof(float);
+    if (!(q.lds <= 160 * 1024 && (size_t)g.B * I * g.OH * g.OW * 4 < ((size_t)1 << 31) &&
+          (size_t)g.B * g.Cin * g.H * g.W * 4 < ((size_t)1 << 31)))
+        return false;
+    return (I == 32 && g.Cin == 3 && q.p == 32) || (I == 64 && g.Cin == 1 && q.p == 16) ||
+           (I == 32 && g.Cin == 1 && q.p == 32) || (I == 32 && g.Cin == 1 && q.p == 16);
+}
+
+// ---- which launch a wgrad-form call takes (conv_wgrad_impl switches on it, mvae_conv_k4_route reports it); splits: the
+//      partials the finish launch sums (1: none) ----
+struct ConvWgradRoute { int route; int splits; Plan pl; WgradPatchGeo wg; Sc2Geo sc2; };
+inline ConvWgradRoute conv_wgrad_route(const ConvGeom &g, const float *dy, const float *x, void *ws, size_t ws_bytes) {
+    ConvWgradRoute r;
+    const int I = g.Cout, J = g.Cin * 16, K = g.B * g.OH * g.OW;
+    if (wgrad_smallcin_ok(g) && !MVAE_TUNE(wm) && !MVAE_TUNE(splits) && ws) {
+        const int blocks = wgrad_smallcin_blocks(g);
+        if (ws_bytes >= (size_t)blocks * I * J * sizeof(float)) {
+            r.route = wgrad_smallcin2_plan(g, r.sc2) ? MVAE_ROUTE_WGRAD_SMALLCIN2 : MVAE_ROUTE_WGRAD_SMALLCIN;
+            r.splits = blocks;
+            return r;
+        }
+    }
+    if (g.stride == 2 && g.pad == 1 && !MVAE_TUNE(wm) && !MVAE_TUNE(splits)) {
+        // both operands in their natural layout through LDS-DMA (wgrad_patch.h): the 8 x 8 and 16 x 16 lattices
+        if (wgrad_patch_plan(g.B, g.Cout, g.Cin, g.OH, g.OW, dy, x, ws, ws_bytes, &r.wg)) {
+            r.route = MVAE_ROUTE_WGRAD_PATCH;
+            r.splits = r.wg.splits;
+            return r;
+        }
+    }
+    r.pl = make_plan(I, J, K, true, PLAN_CONV_WGRAD);
+    r.pl.xcd = MVAE_WGRAD_XCD ? 4 : 0;                          // the tiles of one k range on one XCD (igemm_kernel)
+    r.route = MVAE_ROUTE_IGEMM;
+    r.splits = r.pl.splits;
+    if (r.pl.splits > 1 && (!ws || ws_bytes < r.pl.splits * make_sink(ws, I, J, false).stride * sizeof(float))) r.route = MVAE_ERR_WS;
+    return r;
+}
+
 // ---- conv wgrad form: dw[co][(ci,kh,kw)] = sum_(n,oh,ow) dy[n][co][oh][ow] * x[n][ci][ih][iw] ----
 int conv_wgrad_impl(const float *dy, const float *x, float *dw, ConvGeom g, int flags, void *ws,
                     size_t ws_bytes, hipStream_t st) {
@@ -2416,20 +2568,14 @@ int conv_wgrad_impl(const float *dy, const float *x, float *dw, ConvGeom g, int 
     e.out = dw; e.act = nullptr; e.ld = J; e.bias = nullptr; e.dpre = nullptr; e.ldp = 0;
     e.mask = nullptr; e.ldm = 0; e.mask_scale = 1.f; e.I = I; e.J = J;
     e.accumulate = (flags & MVAE_ACCUMULATE) ? 1 : 0;
-    if (wgrad_smallcin_ok(g) && !MVAE_TUNE(wm) && !MVAE_TUNE(splits) && ws) {
-        const int blocks = wgrad_smallcin_blocks(g);
-        if (ws_bytes >= (size_t)blocks * I * J * sizeof(float)) {
-            const int mt = I / 32, nt = (J + 31) / 32;
-            bool launched = false;
-            if (MVAE_SC2) {
-                int xw = g.W + 8;
-                if (((xw / 4) & 1) == 0) xw += 4;                       // pitch = 4 x odd: the tap columns of a tile hit 32 banks
-                const int p = g.OW <= 16 ? 16 : 32;
-                const size_t stage_f = (size_t)I * p + (size_t)g.Cin * 4 * xw;
-                const size_t red_f = (size_t)(SC2_WAVES - 1) * mt * nt * 1024;
-                size_t lds2 = (size_t)SC2_WAVES * MVAE_SC2_STAGES * stage_f;
-                if (red_f > lds2) lds2 = red_f;
-                lds2 *= sizeof(float);
+    const ConvWgradRoute r = conv_wgrad_route(g, dy, x, ws, ws_bytes);
+    if (r.route < 0) return r.route;
+    if (r.route == MVAE_ROUTE_WGRAD_SMALLCIN2 || r.route == MVAE_ROUTE_WGRAD_SMALLCIN) {
+        const int blocks = r.splits;
+        const int mt = I / 32, nt = (J + 31) / 32;
+        if (r.route == MVAE_ROUTE_WGRAD_SMALLCIN2) {
+            const int xw = r.sc2.xw, p = r.sc2.p;
+            const size_t lds2 = r.sc2.lds;
 #define MVAE_SC2L(MT_, NT_, CI_, P_)                                                                        \
     {                                                                                                       \
         auto kern = wgrad_smallcin2_kernel<MT_, NT_, CI_, P_, MVAE_SC2_STAGES>;                             \
@@ -2440,18 +2586,13 @@ int conv_wgrad_impl(const float *dy, const float *x, float *dw, ConvGeom g, int 
             attr_done = true;                                                                               \
         }                                                                                                   \
         hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * SC2_WAVES), lds2, st, dy, x, (float *)ws, g, g.B * g.OH, xw); \
-        launched = true;                                                                                    \
     }
-                if (lds2 <= 160 * 1024 && (size_t)g.B * I * g.OH * g.OW * 4 < ((size_t)1 << 31) &&
-                    (size_t)g.B * g.Cin * g.H * g.W * 4 < ((size_t)1 << 31)) {
-                    if (I == 32 && g.Cin == 3 && p == 32) MVAE_SC2L(1, 2, 3, 32)
-                    else if (I == 64 && g.Cin == 1 && p == 16) MVAE_SC2L(2, 1, 1, 16)
-                    else if (I == 32 && g.Cin == 1 && p == 32) MVAE_SC2L(1, 1, 1, 32)
-                    else if (I == 32 && g.Cin == 1 && p == 16) MVAE_SC2L(1, 1, 1, 16)
-                }
+            if (I == 32 && g.Cin == 3 && p == 32) MVAE_SC2L(1, 2, 3, 32)
+            else if (I == 64 && g.Cin == 1 && p == 16) MVAE_SC2L(2, 1, 1, 16)
+            else if (I == 32 && g.Cin == 1 && p == 32) MVAE_SC2L(1, 1, 1, 32)
+            else MVAE_SC2L(1, 1, 1, 16)                 // I == 32, Cin == 1, p == 16 (wgrad_smallcin2_plan admits no other)
 #undef MVAE_SC2L
-            }
-            if (!launched) {
+        } else {
             const size_t wave_b = ((size_t)I * SC_DW + 16 * SC_XW) * sizeof(float);
             const size_t red_b = (size_t)(SC_WAVES - 1) * mt * nt * 1024 * sizeof(float);
             const size_t lds = SC_WAVES * wave_b > red_b ? SC_WAVES * wave_b : red_b;
@@ -2471,41 +2612,34 @@ int conv_wgrad_impl(const float *dy, const float *x, float *dw, ConvGeom g, int 
             else if (nt == 1) MVAE_SC(2, 1)
             else MVAE_SC(2, 2)
 #undef MVAE_SC
-            }
-            SplitSink fs = make_sink(ws, I, J, false);
-            if (blocks > 16 && blocks <= 1024 && MVAE_SC2) {
-                hipLaunchKernelGGL((finish_wide_kernel<EpRowMajor>), dim3((J + 31) / 32, I), dim3(1024), 0, st, fs, blocks, e);
-            } else if (blocks > 16) {
-                hipLaunchKernelGGL((finish_kernel<EpRowMajor>), dim3((J + 31) / 32, I), dim3(256), 0, st, fs, blocks, e);
-            } else {
-                hipLaunchKernelGGL((finish_few_kernel<EpRowMajor>), dim3((J + 255) / 256, I), dim3(256), 0, st, fs,
-                                   blocks, e);
-            }
-            return mvae_launch_status();
         }
-    }
-    if (g.stride == 2 && g.pad == 1 && !MVAE_TUNE(wm) && !MVAE_TUNE(splits)) {
-        // both operands in their natural layout through LDS-DMA (wgrad_patch.h): the 8 x 8 and 16 x 16 lattices
-        WgradPatchGeo wg;
-        if (wgrad_patch_plan(g.B, g.Cout, g.Cin, g.OH, g.OW, dy, x, ws, ws_bytes, &wg)) {
-            launch_wgrad_patch(wg, dy, x, st);
-            SplitSink fs = make_sink(ws, I, J, false);
-            if (wg.splits > 64)
-                hipLaunchKernelGGL((finish_wide_kernel<EpRowMajor>), dim3((J + 31) / 32, I), dim3(1024), 0, st, fs, wg.splits, e);
-            else if (wg.splits > 16)         // (the 1024-thread form issues 32 loads per thread whatever the count)
-                hipLaunchKernelGGL((finish_kernel<EpRowMajor>), dim3((J + 31) / 32, I), dim3(256), 0, st, fs, wg.splits, e);
-            else
-                hipLaunchKernelGGL((finish_few_kernel<EpRowMajor>), dim3((J + 255) / 256, I), dim3(256), 0, st, fs, wg.splits, e);
-            return mvae_launch_status();
+        SplitSink fs = make_sink(ws, I, J, false);
+        if (blocks > 16 && blocks <= 1024 && MVAE_SC2) {
+            hipLaunchKernelGGL((finish_wide_kernel<EpRowMajor>), dim3((J + 31) / 32, I), dim3(1024), 0, st, fs, blocks, e);
+        } else if (blocks > 16) {
+            hipLaunchKernelGGL((finish_kernel<EpRowMajor>), dim3((J + 31) / 32, I), dim3(256), 0, st, fs, blocks, e);
+        } else {
+            hipLaunchKernelGGL((finish_few_kernel<EpRowMajor>), dim3((J + 255) / 256, I), dim3(256), 0, st, fs,
+                               blocks, e);
         }
+        return mvae_launch_status();
     }
-    Plan pl = make_plan(I, J, K, true, PLAN_CONV_WGRAD);
-    pl.xcd = MVAE_WGRAD_XCD ? 4 : 0;                            // the tiles of one k range on one XCD (igemm_kernel)
+    if (r.route == MVAE_ROUTE_WGRAD_PATCH) {
+        const WgradPatchGeo &wg = r.wg;
+        launch_wgrad_patch(wg, dy, x, st);
+        SplitSink fs = make_sink(ws, I, J, false);
+        if (wg.splits > 64)
+            hipLaunchKernelGGL((finish_wide_kernel<EpRowMajor>), dim3((J + 31) / 32, I), dim3(1024), 0, st, fs, wg.splits, e);
+        else if (wg.splits > 16)         // (the 1024-thread form issues 32 loads per thread whatever the count)
+            hipLaunchKernelGGL((finish_kernel<EpRowMajor>), dim3((J + 31) / 32, I), dim3(256), 0, st, fs, wg.splits, e);
+        else
+            hipLaunchKernelGGL((finish_few_kernel<EpRowMajor>), dim3((J + 255) / 256, I), dim3(256), 0, st, fs, wg.splits, e);
+        return mvae_launch_status();
+    }
     SplitSink sink = make_sink(ws, I, J, false);
-    if (pl.splits > 1 && (!ws || ws_bytes < pl.splits * sink.stride * sizeof(float))) return MVAE_ERR_WS;
     auto mp = [&](auto &p) { p.dy = dy; p.g = g; };
     auto mq = [&](auto &q) { q.x = x; q.g = g; q.J = J; };
-    return launch_igemm<LdWgradDy, LdWgradX, EpRowMajor, false>(pl, mp, mq, e, I, J, K, sink, st);
+    return launch_igemm<LdWgradDy, LdWgradX, EpRowMajor, false>(r.pl, mp, mq, e, I, J, K, sink, st);
 }
 
 }  // namespace
@@ -2648,4 +2782,50 @@ MVAE_EXPORT int mvae_convT2d_k4_wgrad(const float *dy, const float *x, float *dw
     if (!dy || !x || !dw || B <= 0 || !convT_geom(B, Cin, H, W, Cout, stride, pad, &g)) return MVAE_ERR_ARG;
     // mirrored conv: "dy" operand is the transpose's input x, "x" operand is the transpose's dy
     return conv_wgrad_impl(x, dy, dw, g, flags, ws, ws_bytes, (hipStream_t)stream);
+}
+
+// ---- which launch a call would take: the route functions the launches themselves switch on, on stand-in operands that
+//      are 16-byte aligned and never dereferenced.  Pure host code. ----
+MVAE_EXPORT int mvae_conv_k4_route(int op, int B, int Cin, int H, int W, int Cout, int stride, int pad, size_t ws_bytes,
+                                   int *splits) {
+    float *const a = reinterpret_cast<float *>((uintptr_t)1 << 20);      // stands for every operand
+    void *const ws = ws_bytes ? (void *)a : nullptr;
+    ConvGeom g;
+    int route = MVAE_ERR_ARG, sp = 1;
+    if (B <= 0) return MVAE_ERR_ARG;
+    switch (op) {
+        case MVAE_OP_CONV_FWD: case MVAE_OP_CONV_DGRAD: case MVAE_OP_CONV_WGRAD:
+            if (!conv_args_ok(B, Cin, H, W, Cout, stride, pad)) return MVAE_ERR_ARG;
+            g = make_geom(B, Cin, H, W, Cout, stride, pad);
+            break;
+        case MVAE_OP_CONVT_FWD: case MVAE_OP_CONVT_FWD_STATS: case MVAE_OP_CONVT_DGRAD: case MVAE_OP_CONVT_WGRAD:
+            if (!convT_geom(B, Cin, H, W, Cout, stride, pad, &g)) return MVAE_ERR_ARG;
+            break;
+        default: return MVAE_ERR_ARG;
+    }
+    switch (op) {
+        case MVAE_OP_CONV_FWD: case MVAE_OP_CONVT_DGRAD:
+            route = conv_fwd_route(g, a, a, a, nullptr, nullptr, false).route;    // (false: a query allocates nothing)
+            break;
+        case MVAE_OP_CONV_DGRAD: case MVAE_OP_CONVT_FWD: {
+            const ConvDgradRoute r = conv_dgrad_route(g, a, a, a, a, nullptr, nullptr);
+            route = r.route;
+            const bool direct = route != MVAE_ROUTE_IGEMM && route != MVAE_ROUTE_IGEMM_PAIR && route != MVAE_ROUTE_PATCH8 &&
+                                route != MVAE_ROUTE_PATCH7 && route != MVAE_ROUTE_PATCH16;
+            if (!direct && ws_bytes < dgrad_ws_floats(g) * sizeof(float)) route = MVAE_ERR_WS;
+            break;
+        }
+        case MVAE_OP_CONVT_FWD_STATS:
+            if (!conv_dgrad_stats_tiles(g)) return MVAE_ERR_ARG;
+            if (ws_bytes < dgrad_ws_floats(g) * sizeof(float)) return MVAE_ERR_WS;
+            route = conv_dgrad_stats_route(g, a, a).route;
+            break;
+        default: {  // the two weight gradients: the same launch (the transposed conv's operands swapped)
+            const ConvWgradRoute r = conv_wgrad_route(g, a, a, ws, ws_bytes);
+            route = r.route; sp = r.splits;
+            break;
+        }
+    }
+    if (route > 0 && splits) *splits = sp;
+    return route;
 }

@@ -354,6 +354,21 @@ def conv_repack_batched(items):
         check(_lib.lib().mvae_conv_k4_repack_batched(arr, len(chunk), _stream()), 'mvae_conv_k4_repack_batched')
 
 
+def conv_route(op, B, Cin, H, W, Cout, stride, pad, ws_bytes=None):
+    """(route, splits) of the launch ``op`` (a key of ``_lib.CONV_OPS``) on this geometry -- B, Cin, H, W, Cout as that
+    launch's own arguments, i.e. the module's channels and its INPUT map: the name of the kernel it takes
+    (``_lib.CONV_ROUTES``) and the number of partials its finish launch sums (1: none).  Host only (mvae_conv_k4_route:
+    the decision function the launch itself switches on, for 16-byte-aligned operands).  ``ws_bytes``: the scratch the
+    launch gets, by default what the wrappers here pass before anything asked for more (``_WS_MIN_BYTES``).  Raises
+    where the launch would refuse the arguments."""
+    n = ctypes.c_int(1)
+    rc = _lib.lib().mvae_conv_k4_route(_lib.CONV_OPS[op], B, Cin, H, W, Cout, stride, pad,
+                                       _WS_MIN_BYTES if ws_bytes is None else int(ws_bytes), ctypes.byref(n))
+    if rc <= 0:
+        check(rc if rc < 0 else -1, 'mvae_conv_k4_route')
+    return _lib.CONV_ROUTES[rc], n.value
+
+
 def conv2d_wgrad(dy, x, dw, stride, pad, accumulate=False):
     _need_gpu(dy, x, dw); _f32c(dy, x, dw)
     B, Cin, H, W = x.shape

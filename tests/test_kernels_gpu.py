@@ -23,6 +23,12 @@ def dev(t):
     return None if t is None else t.to(DEV)
 
 
+def nans(*shape):
+    """An output tensor no kernel has written: a region a launch skips shows as NaN (torch.empty can hand back the
+    previous call's correct result)."""
+    return torch.full(shape, float('nan'), device=DEV)
+
+
 def swish(x):
     return x * torch.sigmoid(x)
 
@@ -270,6 +276,11 @@ def test_linear_strided_views():
 
 
 # ----------------------------------------------------------------------------- Conv / ConvT
+# Batches of 1-130: the direct <= 4-channel kernels, the stride-1 kernel and the gather launches (igemm_kernel) at small
+# sizes.  They do NOT reach convT_patch2_kernel (from 64-668 images, by layer), wgrad_patch_kernel (from 16 images of the
+# model layers; these stop at 3), conv_small_fwd_kernel<., 32> (from 1024 blocks), the (32, 1, p32) / (32, 1, p16) forms of
+# wgrad_smallcin2_kernel or the older wgrad_smallcin_kernel: tests/test_conv_routes_gpu.py runs those, each case asserting
+# through kernels.conv_route which kernel it is on.
 CONV_CASES = [(4, 3, 64, 32, 2, 1), (3, 32, 32, 64, 2, 1), (2, 64, 16, 128, 2, 1), (2, 128, 8, 256, 1, 0),
               (5, 1, 28, 64, 2, 1), (2, 64, 14, 128, 2, 1), (1, 5, 6, 7, 1, 0), (3, 2, 4, 3, 2, 1),
               (130, 3, 64, 32, 2, 1), (37, 1, 28, 64, 2, 1)]      # more (image, row) units than waves of the small-Cin wgrad
@@ -385,21 +396,23 @@ def test_conv2d(B, Cin, H, Cout, s, p):
     y = F.conv2d(x, w, None, s, p)
     dy = g(*y.shape, seed=22)
     y.backward(dy)
-    pre = torch.empty(*y.shape, device=DEV); act = torch.empty(*y.shape, device=DEV)
+    pre = nans(*y.shape); act = nans(*y.shape)
     K.conv2d_fwd(dev(x.detach()), dev(w.detach()), pre, act, s, p)
     assert_close(pre, y, 'conv fwd')
     assert_close(act, swish(y.detach()), 'conv fwd act')
-    dx = torch.empty(*x.shape, device=DEV)
+    dx = nans(*x.shape)
     K.conv2d_dgrad(dev(dy), dev(w.detach()), dx, None, s, p)
     assert_close(dx, x.grad, 'conv dgrad')
     pre_in = g(*x.shape, seed=23)
-    K.conv2d_dgrad(dev(dy), dev(w.detach()), dx, dev(pre_in), s, p)
-    assert_close(dx, x.grad * swish_grad(pre_in), 'conv dgrad * swish\'')
-    dw = torch.empty(*w.shape, device=DEV)
+    dx2 = nans(*x.shape)
+    K.conv2d_dgrad(dev(dy), dev(w.detach()), dx2, dev(pre_in), s, p)
+    assert_close(dx2, x.grad * swish_grad(pre_in), 'conv dgrad * swish\'')
+    dw = nans(*w.shape)
     K.conv2d_wgrad(dev(dy), dev(x.detach()), dw, s, p)
     assert_close(dw, w.grad, 'conv wgrad')
-    K.conv2d_wgrad(dev(dy), dev(x.detach()), dw, s, p, accumulate=True)
-    assert_close(dw, 2 * w.grad, 'conv wgrad accumulate')
+    dw2 = dev(w.grad.clone())
+    K.conv2d_wgrad(dev(dy), dev(x.detach()), dw2, s, p, accumulate=True)
+    assert_close(dw2, 2 * w.grad, 'conv wgrad accumulate')
 
 
 @pytest.mark.parametrize('B,Cin,H,Cout', [(2049, 6, 14, 1), (2049, 8, 14, 1), (2047, 64, 14, 1), (512, 8, 32, 3), (1024, 4, 28, 2)])
@@ -413,13 +426,13 @@ def test_small_channel_transposed_conv_through_lds(B, Cin, H, Cout):
     x = g(B, Cin, H, H, seed=40)
     w = g(Cin, Cout, 4, 4, seed=41, scale=(Cin * 4) ** -0.5)
     y = F.conv_transpose2d(x, w, None, 2, 1)
-    pre = torch.empty(*y.shape, device=DEV); act = torch.empty(*y.shape, device=DEV)
+    pre = nans(*y.shape); act = nans(*y.shape)
     K.convT2d_fwd(dev(x), dev(w), pre, act, 2, 1)
     assert_close(pre, y, 'convT fwd through LDS')
     assert_close(act, swish(y), 'convT fwd through LDS, act')
     # Conv2d(Cout, Cin): its data gradient is the same launch on dy = x
     pre_in = g(*y.shape, seed=42)
-    dx = torch.empty(*y.shape, device=DEV)
+    dx = nans(*y.shape)
     K.conv2d_dgrad(dev(x), dev(w), dx, dev(pre_in), 2, 1)
     assert_close(dx, y * swish_grad(pre_in), "conv dgrad * swish' through LDS")
 
@@ -436,14 +449,18 @@ def test_conv_transpose2d(B, Cin, H, Cout, s, p):
     y = F.conv_transpose2d(x, w, None, s, p)
     dy = g(*y.shape, seed=32)
     y.backward(dy)
-    pre = torch.empty(*y.shape, device=DEV); act = torch.empty(*y.shape, device=DEV)
+    pre = nans(*y.shape); act = nans(*y.shape)
     K.convT2d_fwd(dev(x.detach()), dev(w.detach()), pre, act, s, p)
     assert_close(pre, y, 'convT fwd')
     assert_close(act, swish(y.detach()), 'convT fwd act')
-    dx = torch.empty(*x.shape, device=DEV)
+    dx = nans(*x.shape)
     K.convT2d_dgrad(dev(dy), dev(w.detach()), dx, None, s, p)
     assert_close(dx, x.grad, 'convT dgrad')
-    dw = torch.empty(*w.shape, device=DEV)
+    pre_in = g(*x.shape, seed=33)           # the producer's Swish' folded in: FashionMNIST's decoder runs this form
+    dx2 = nans(*x.shape)
+    K.convT2d_dgrad(dev(dy), dev(w.detach()), dx2, dev(pre_in), s, p)
+    assert_close(dx2, x.grad * swish_grad(pre_in), 'convT dgrad * swish\'')
+    dw = nans(*w.shape)
     K.convT2d_wgrad(dev(dy), dev(x.detach()), dw, s, p)
     assert_close(dw, w.grad, 'convT wgrad')
 
