@@ -254,6 +254,46 @@ int mvae_conv_k4_route(int op, int B, int Cin, int H, int W, int Cout, int strid
                        size_t ws_bytes, int *splits /* may be NULL */);
 
 /* ------------------------------------------------------------------------------------
+ * K17 General stride-2 conv family (csrc/conv_gen.hip): Conv2d / ConvTranspose2d with a square kernel
+ *     ks in {4, 5}, stride 2, pad in {0, 1}, bias=False, ANY map size (odd, non-square) with
+ *     H + 2 pad >= ks and W + 2 pad >= ks (Conv2d) or H, W >= 1 (ConvTranspose2d, output_padding 0):
+ *     the image stacks of multimnist/model.py:78-84 (Conv2d(32,64,4,2,1) on 25 x 25, Conv2d(128,256,4,2,0))
+ *     and :120-128 (ConvTranspose2d(256,128,4,2,0), ConvTranspose2d(64,32,5,2,1)).
+ *     Same contracts as the k4 launches above, argument for argument, with `ks` next to stride and pad:
+ *     forward writes pre and / or act = swish(pre); the data gradients multiply by swish'(pre_in) when given;
+ *     the weight gradients overwrite or (MVAE_ACCUMULATE) add.  Exact fp32 MFMA, no atomics, deterministic.
+ *     Anything outside the domain -- other ks / stride / pad, a tensor of 2^28 elements or more (32-bit byte
+ *     offsets) -- is MVAE_ERR_ARG.  Geometries the k4 family covers are accepted too, but the Python layers
+ *     never send those here.  The two launches that take `ws` without being weight gradients (Conv2d data gradient,
+ *     ConvTranspose2d forward) make a class-major copy of the weights there (MVAE_ERR_WS if it does not fit).
+ *   mvae_conv_gen_ws_bytes   scratch the launch `op` (MVAE_OP_*, B, Cin, H, W, Cout as that launch's own
+ *                            arguments) needs: the partial slabs of a split weight gradient, the weight copy of the
+ *                            two launches above (Cin * Cout * ks * ks floats), 0 for the others.
+ *   mvae_conv_gen_supported  1 / 0: the predicate the launches apply (transposed: 0 Conv2d, 1 ConvTranspose2d).
+ *   Both are host only.
+ * ---------------------------------------------------------------------------------- */
+int mvae_conv2d_gen_fwd(const float *x, const float *w, float *pre, float *act,
+                        int B, int Cin, int H, int W, int Cout, int ks, int stride, int pad,
+                        mvae_stream_t stream);
+int mvae_conv2d_gen_dgrad(const float *dy, const float *w, float *dx, const float *pre_in,
+                          int B, int Cin, int H, int W, int Cout, int ks, int stride, int pad,
+                          void *ws, size_t ws_bytes, mvae_stream_t stream);
+int mvae_conv2d_gen_wgrad(const float *dy, const float *x, float *dw,
+                          int B, int Cin, int H, int W, int Cout, int ks, int stride, int pad,
+                          int flags, void *ws, size_t ws_bytes, mvae_stream_t stream);
+int mvae_convT2d_gen_fwd(const float *x, const float *w, float *pre, float *act,
+                         int B, int Cin, int H, int W, int Cout, int ks, int stride, int pad,
+                         void *ws, size_t ws_bytes, mvae_stream_t stream);
+int mvae_convT2d_gen_dgrad(const float *dy, const float *w, float *dx, const float *pre_in,
+                           int B, int Cin, int H, int W, int Cout, int ks, int stride, int pad,
+                           mvae_stream_t stream);
+int mvae_convT2d_gen_wgrad(const float *dy, const float *x, float *dw,
+                           int B, int Cin, int H, int W, int Cout, int ks, int stride, int pad,
+                           int flags, void *ws, size_t ws_bytes, mvae_stream_t stream);
+size_t mvae_conv_gen_ws_bytes(int op, int B, int Cin, int H, int W, int Cout, int ks, int stride, int pad);
+int mvae_conv_gen_supported(int transposed, int B, int Cin, int H, int W, int Cout, int ks, int stride, int pad);
+
+/* ------------------------------------------------------------------------------------
  * K4  BatchNorm2d / BatchNorm1d (training mode, eps 1e-5, momentum 0.1) + fused Swish:
  *     celeba/model.py:80,83,86,118,121,124,149,152,176,179,182; celeba19/model.py:106,109,
  *     112,144,147,150.  x is [G*B, C, HW] (HW = 1 for BatchNorm1d): G independent groups

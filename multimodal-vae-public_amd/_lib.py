@@ -132,6 +132,15 @@ _SIGNATURES = {
     'mvae_convT2d_k4_stats_tiles': (c_size_t, [c_int] * 7),
     'mvae_convT2d_k4_fwd_stats': (c_int, [P, P, P, c_size_t] + [c_int] * 7 + [P, c_size_t, P]),
     'mvae_conv_k4_route': (c_int, [c_int] * 8 + [c_size_t, ctypes.POINTER(c_int)]),
+    # K17: the general stride-2 conv family (ks in {4, 5}, pad in {0, 1}, any map size)
+    'mvae_conv2d_gen_fwd': (c_int, [P, P, P, P] + [c_int] * 8 + [P]),
+    'mvae_conv2d_gen_dgrad': (c_int, [P, P, P, P] + [c_int] * 8 + [P, c_size_t, P]),
+    'mvae_conv2d_gen_wgrad': (c_int, [P, P, P] + [c_int] * 9 + [P, c_size_t, P]),
+    'mvae_convT2d_gen_fwd': (c_int, [P, P, P, P] + [c_int] * 8 + [P, c_size_t, P]),
+    'mvae_convT2d_gen_dgrad': (c_int, [P, P, P, P] + [c_int] * 8 + [P]),
+    'mvae_convT2d_gen_wgrad': (c_int, [P, P, P] + [c_int] * 9 + [P, c_size_t, P]),
+    'mvae_conv_gen_ws_bytes': (c_size_t, [c_int] * 9),
+    'mvae_conv_gen_supported': (c_int, [c_int] * 9),
     'mvae_bn_stats_merge': (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P, c_float, c_float, c_int, P, P]),
     'mvae_linear_wgrad_batched': (c_int, [ctypes.POINTER(WgradItem), c_int, P]),
     'mvae_linear_wgrad_batched_adam': (c_int, [ctypes.POINTER(WgradItem), c_int, ctypes.POINTER(AdamFuse), P]),

@@ -7,6 +7,7 @@ the latent path of ``MVAE.forward``.  Every ``Function`` is a thin shell over HI
     elbo_loss (bimodal, label)        mnist/train.py:20-59, fashionmnist/train.py:20-59
     elbo_loss (bimodal, attributes)   celeba/train.py:22-65
     elbo_loss (N-modal lists)         celeba19/train.py:26-60
+    elbo_loss (bimodal, digit string) multimnist/train.py:22-68
 
 The fused train step (``engine.py``) does not go through these: it launches the same kernels
 directly with the loss gradient folded into the forward pass.
@@ -346,3 +347,43 @@ def elbo_loss_multi(recon, data, mu, logvar, lambda_image=1.0, lambda_attrs=1.0,
         rows.append(_BceRowsFn.apply(x, t)); weights.append(float(lambda_attrs))
     rows.append(_KlRowsFn.apply(mu, logvar)); weights.append(_w(annealing_factor))
     return _WeightedMeanFn.apply(weights, *rows)
+
+
+class _WeightedSumsFn(torch.autograd.Function):
+    """sum_i (w_i / B) * sum(rows_i) for row vectors of DIFFERENT lengths: ``_WeightedMeanFn`` for terms that hold
+    several rows per sample (the 4 character positions of MultiMNIST's text term) -- the mean over the batch of a
+    per-sample sum is the sum of all rows over B."""
+
+    @staticmethod
+    def forward(ctx, weights, B, *rows):
+        dev = rows[0].device
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+        coefs = _coef_tensor(weights, B, dev)
+        for i, r in enumerate(rows):
+            K.group_sums(r.contiguous(), coefs[i:i + 1], None, out, 1, r.numel(), accumulate=(i > 0))
+        ctx.coefs, ctx.lens = coefs, [r.numel() for r in rows]
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        return (None, None) + tuple((g * ctx.coefs[i]).expand(n) for i, n in enumerate(ctx.lens))
+
+
+def elbo_loss_text(recon_image, image, recon_text, text, mu, logvar,
+                   lambda_image=1.0, lambda_text=1.0, annealing_factor=1):
+    """multimnist/train.py:22-68: image BCE summed over the 2500 pixels, cross-entropy of the [B, 4, 12] text logits
+    summed over the classes and the 4 positions (:53-61), KL rows, weighted mean over the batch."""
+    _need_gpu(mu)
+    B = mu.size(0)
+    rows, weights = [], []
+    if recon_image is not None and image is not None:
+        rows.append(_image_rows(recon_image, image)); weights.append(float(lambda_image))
+    if recon_text is not None and text is not None:
+        logits = recon_text.reshape(-1, recon_text.size(2)).contiguous()
+        labels = text.reshape(-1).contiguous()
+        if not (labels.size(0) == logits.size(0)):
+            raise ValueError("Target size ({}) must be the same as input size ({})".format(
+                labels.size(0), logits.size(0)))
+        rows.append(_CeRowsFn.apply(logits, labels)); weights.append(float(lambda_text))
+    rows.append(_KlRowsFn.apply(mu, logvar)); weights.append(_w(annealing_factor))
+    return _WeightedSumsFn.apply(weights, B, *rows)

@@ -442,6 +442,68 @@ def convT2d_wgrad(dy, x, dw, stride, pad, accumulate=False):
           'mvae_convT2d_k4_wgrad')
 
 
+# ---------------------------------------------------------------------------- general stride-2 convs (K17)
+def conv_gen_supported(transposed, B, Cin, H, W, Cout, ks, stride, pad):
+    """Whether the general stride-2 family (csrc/conv_gen.hip) runs this geometry -- B, Cin, H, W, Cout as the
+    forward launch's own arguments.  Host only: the predicate the launches themselves apply."""
+    return bool(_lib.lib().mvae_conv_gen_supported(1 if transposed else 0, B, Cin, H, W, Cout, ks, stride, pad))
+
+
+def _gen_ws(op, dev, B, Cin, H, W, Cout, ks, stride, pad):
+    nbytes = _lib.lib().mvae_conv_gen_ws_bytes(_lib.CONV_OPS[op], B, Cin, H, W, Cout, ks, stride, pad)
+    return _ws_args(nbytes, dev)
+
+
+def conv2d_gen_fwd(x, w, pre, act, stride, pad):
+    """x[B,Cin,H,W], w[Cout,Cin,ks,ks] -> [B,Cout,(H+2p-ks)//2+1, ...]"""
+    _need_gpu(x, w, pre, act); _f32c(x, w, pre, act)
+    B, Cin, H, W = x.shape
+    check(_lib.lib().mvae_conv2d_gen_fwd(_ptr(x), _ptr(w), _ptr(pre), _ptr(act), B, Cin, H, W, w.shape[0], w.shape[2],
+                                         stride, pad, _stream()), 'mvae_conv2d_gen_fwd')
+
+
+def conv2d_gen_dgrad(dy, w, dx, pre_in, stride, pad):
+    _need_gpu(dy, w, dx, pre_in); _f32c(dy, w, dx, pre_in)
+    B, Cin, H, W = dx.shape
+    ws, wsb = _gen_ws('conv_dgrad', dy.device, B, Cin, H, W, w.shape[0], w.shape[2], stride, pad)
+    check(_lib.lib().mvae_conv2d_gen_dgrad(_ptr(dy), _ptr(w), _ptr(dx), _ptr(pre_in), B, Cin, H, W, w.shape[0], w.shape[2],
+                                           stride, pad, ws, wsb, _stream()), 'mvae_conv2d_gen_dgrad')
+
+
+def conv2d_gen_wgrad(dy, x, dw, stride, pad, accumulate=False):
+    _need_gpu(dy, x, dw); _f32c(dy, x, dw)
+    B, Cin, H, W = x.shape
+    Cout, ks = dw.shape[0], dw.shape[2]
+    ws, wsb = _gen_ws('conv_wgrad', dy.device, B, Cin, H, W, Cout, ks, stride, pad)
+    check(_lib.lib().mvae_conv2d_gen_wgrad(_ptr(dy), _ptr(x), _ptr(dw), B, Cin, H, W, Cout, ks, stride, pad,
+                                           ACCUMULATE if accumulate else 0, ws, wsb, _stream()), 'mvae_conv2d_gen_wgrad')
+
+
+def convT2d_gen_fwd(x, w, pre, act, stride, pad):
+    """x[B,Cin,H,W], w[Cin,Cout,ks,ks] -> [B,Cout,(H-1)*2-2p+ks, ...]"""
+    _need_gpu(x, w, pre, act); _f32c(x, w, pre, act)
+    B, Cin, H, W = x.shape
+    ws, wsb = _gen_ws('convT_fwd', x.device, B, Cin, H, W, w.shape[1], w.shape[2], stride, pad)
+    check(_lib.lib().mvae_convT2d_gen_fwd(_ptr(x), _ptr(w), _ptr(pre), _ptr(act), B, Cin, H, W, w.shape[1], w.shape[2],
+                                          stride, pad, ws, wsb, _stream()), 'mvae_convT2d_gen_fwd')
+
+
+def convT2d_gen_dgrad(dy, w, dx, pre_in, stride, pad):
+    _need_gpu(dy, w, dx, pre_in); _f32c(dy, w, dx, pre_in)
+    B, Cin, H, W = dx.shape
+    check(_lib.lib().mvae_convT2d_gen_dgrad(_ptr(dy), _ptr(w), _ptr(dx), _ptr(pre_in), B, Cin, H, W, w.shape[1], w.shape[2],
+                                            stride, pad, _stream()), 'mvae_convT2d_gen_dgrad')
+
+
+def convT2d_gen_wgrad(dy, x, dw, stride, pad, accumulate=False):
+    _need_gpu(dy, x, dw); _f32c(dy, x, dw)
+    B, Cin, H, W = x.shape
+    Cout, ks = dw.shape[1], dw.shape[2]
+    ws, wsb = _gen_ws('convT_wgrad', dy.device, B, Cin, H, W, Cout, ks, stride, pad)
+    check(_lib.lib().mvae_convT2d_gen_wgrad(_ptr(dy), _ptr(x), _ptr(dw), B, Cin, H, W, Cout, ks, stride, pad,
+                                            ACCUMULATE if accumulate else 0, ws, wsb, _stream()), 'mvae_convT2d_gen_wgrad')
+
+
 # ---------------------------------------------------------------------------- BatchNorm
 def bn_train_fwd(x, gamma, beta, y, save_mean, save_invstd, running_mean, running_var, G,
                  eps=1e-5, momentum=0.1, n_updates=1, swish=True, n_updates_dev=None):

@@ -200,11 +200,41 @@ def compile_plan(mods):
     return plan
 
 
+def _k4_module(m):
+    """The module is one the 4x4 family (csrc/conv.hip) is built for."""
+    return (tuple(m.kernel_size) == (4, 4) and m.bias is None and
+            (tuple(m.stride), tuple(m.padding)) in (((2, 2), (1, 1)), ((1, 1), (0, 0))))
+
+
+def _gen_module(m):
+    """The module is one the general stride-2 family (csrc/conv_gen.hip) is built for: the library's own predicate on
+    the smallest map the (kernel, stride, pad) admits -- it refuses other kernel sizes, strides and pads."""
+    ks, s, p = m.kernel_size, m.stride, m.padding
+    if m.bias is not None or ks[0] != ks[1] or s[0] != s[1] or p[0] != p[1]:
+        return False
+    if tuple(getattr(m, 'output_padding', (0, 0))) != (0, 0) or tuple(m.dilation) != (1, 1) or m.groups != 1:
+        return False
+    transposed = isinstance(m, nn.ConvTranspose2d)
+    side = 1 if transposed else max(ks[0] - 2 * p[0], 1)
+    return K.conv_gen_supported(transposed, 1, m.in_channels, side, side, m.out_channels, ks[0], s[0], p[0])
+
+
 def _check_conv(m):
-    ok = (tuple(m.kernel_size) == (4, 4) and m.bias is None and
-          (tuple(m.stride), tuple(m.padding)) in (((2, 2), (1, 1)), ((1, 1), (0, 0))))
-    if not ok:
-        raise RuntimeError('only 4x4 convs with bias=False and (stride,pad) in {(2,1),(1,0)} are built')
+    if not (_k4_module(m) or _gen_module(m)):
+        raise RuntimeError('only 4x4 convs with bias=False and (stride,pad) in {(2,1),(1,0)} (the k4 kernels) or square '
+                           '4x4 / 5x5 convs with bias=False, stride 2 and pad 0 or 1 (the general stride-2 kernels) '
+                           'are built')
+
+
+def _k4_launch(op, H, W):
+    """Whether this launch of a conv op goes to the 4x4 family (H, W: the module's input map) -- everything that family
+    admits does, exactly as before the general family existed; the rest goes to the general stride-2 kernels."""
+    m = op.mod
+    if not _k4_module(m):
+        return False
+    if m.stride[0] == 2 and op.kind == 'conv':
+        return H % 2 == 0 and W % 2 == 0          # conv_args_ok: the stride-2 4x4 kernels take even maps only
+    return True
 
 
 def plan_params(plan):
@@ -317,11 +347,13 @@ def forward_tape(plan, x, groups=1, masks=None, bn_updates=1, training=True, fin
             s, p = m.stride[0], m.padding[0]
             h = h.contiguous()
             Bn, _, H, W = h.shape
+            ks = m.kernel_size[0]
+            k4 = _k4_launch(op, H, W)
             if op.kind == 'conv':
-                Cout, OH, OW = m.out_channels, (H + 2 * p - 4) // s + 1, (W + 2 * p - 4) // s + 1
+                Cout, OH, OW = m.out_channels, (H + 2 * p - ks) // s + 1, (W + 2 * p - ks) // s + 1
             else:
-                Cout, OH, OW = m.out_channels, (H - 1) * s - 2 * p + 4, (W - 1) * s - 2 * p + 4
-            if op.kind == 'convT' and stats_only and STATS_CONV and op_index + 1 == last_bn and not op.act and training:
+                Cout, OH, OW = m.out_channels, (H - 1) * s - 2 * p + ks, (W - 1) * s - 2 * p + ks
+            if k4 and op.kind == 'convT' and stats_only and STATS_CONV and op_index + 1 == last_bn and not op.act and training:
                 tiles = K.convT2d_stats_tiles(h, m.weight, s, p)
                 if tiles > 0 and Bn % groups == 0 and tiles % groups == 0:
                     # the pass ends at the BatchNorm behind this layer and only its statistics are wanted: the launch
@@ -339,7 +371,9 @@ def forward_tape(plan, x, groups=1, masks=None, bn_updates=1, training=True, fin
                 pre = torch.empty(Bn, Cout, OH, OW, dtype=torch.float32, device=h.device)
             if op.act:
                 act = torch.empty(Bn, Cout, OH, OW, dtype=torch.float32, device=h.device)
-            if op.kind == 'conv':
+            if not k4:          # the general stride-2 kernels: no repacked copies, no statistics-only form
+                (K.conv2d_gen_fwd if op.kind == 'conv' else K.convT2d_gen_fwd)(h, m.weight.detach(), pre, act, s, p)
+            elif op.kind == 'conv':
                 K.conv2d_fwd(h, m.weight.detach(), pre, act, s, p)
             else:
                 wr = None
@@ -455,14 +489,20 @@ def backward_tape(plan, tape, g, need_input_grad=False, groups=1, input_grad_out
             s, p = m.stride[0], m.padding[0]
             out_shape = _conv_out_shape(op, x)
             g = g.reshape(out_shape).contiguous()
-            def conv_wgrad(op=op, m=m, g=g, x=x, s=s, p=p):
+            k4 = _k4_launch(op, x.shape[2], x.shape[3])
+            def conv_wgrad(op=op, m=m, g=g, x=x, s=s, p=p, k4=k4):
                 dw, acc = grad_target(m.weight)
-                (K.conv2d_wgrad if op.kind == 'conv' else K.convT2d_wgrad)(g, x, dw, s, p, accumulate=acc)
+                if k4:
+                    (K.conv2d_wgrad if op.kind == 'conv' else K.convT2d_wgrad)(g, x, dw, s, p, accumulate=acc)
+                else:
+                    (K.conv2d_gen_wgrad if op.kind == 'conv' else K.convT2d_gen_wgrad)(g, x, dw, s, p, accumulate=acc)
             side(conv_wgrad)
             if want_dx:
                 dx = torch.empty_like(x)
                 pin = None if pre_in is None else pre_in.reshape(x.shape)
-                if op.kind == 'conv':
+                if not k4:
+                    (K.conv2d_gen_dgrad if op.kind == 'conv' else K.convT2d_gen_dgrad)(g, m.weight.detach(), dx, pin, s, p)
+                elif op.kind == 'conv':
                     key = _probe_repack(m, False, x.shape[0], x.shape[1], x.shape[2], x.shape[3], m.out_channels, s, p)
                     K.conv2d_dgrad(g, m.weight.detach(), dx, pin, s, p, wr=_fresh_repack(m, key))
                 else:
@@ -506,9 +546,10 @@ def _conv_out_shape(op, x):
     m = op.mod
     s, p = m.stride[0], m.padding[0]
     Bn, _, H, W = x.shape
+    ks = m.kernel_size[0]
     if op.kind == 'conv':
-        return (Bn, m.out_channels, (H + 2 * p - 4) // s + 1, (W + 2 * p - 4) // s + 1)
-    return (Bn, m.out_channels, (H - 1) * s - 2 * p + 4, (W - 1) * s - 2 * p + 4)
+        return (Bn, m.out_channels, (H + 2 * p - ks) // s + 1, (W + 2 * p - ks) // s + 1)
+    return (Bn, m.out_channels, (H - 1) * s - 2 * p + ks, (W - 1) * s - 2 * p + ks)
 
 
 # ---- repacked weight copies of the dgrad-form conv launches (Conv2d data gradient, ConvTranspose2d forward).

@@ -1,29 +1,37 @@
-"""The recurrent text stacks of the MultiMNIST MVAE on HIP -- drop-in for the ``TextEncoder`` / ``TextDecoder``
-classes of the reference's ``multimnist/model.py`` ("then MultiMNIST GRU stacks"): same
-constructor arguments, ``forward`` signatures, return values and ``state_dict`` keys
-(``embed.weight``, ``gru.weight_ih_l0`` ... ``gru.bias_hh_l0_reverse``, ``h2p.*`` / ``z2h.*``, ``h2o.*``).
+"""MultiMNIST MVAE (50x50 image of up to four digits + the digit string) on HIP -- drop-in for the reference's
+``multimnist/model.py``: same constructor arguments, ``forward`` signatures, return values and ``state_dict`` keys
+(``image_encoder.features.0.weight`` ... ``image_encoder.classifier.3.bias``, ``image_decoder.upsample.0.*``,
+``image_decoder.hallucinate.*``, ``text_encoder.embed.weight``, ``gru.weight_ih_l0`` ... ``h2o.*``).
 
-    TextEncoder      multimnist/model.py:145-179   q(z|y): Embedding -> bidirectional GRU -> last position,
+    MVAE             multimnist/model.py:21-72     forward / infer / reparametrize, PoE with the prior expert
+    ImageEncoder     multimnist/model.py:75-111    q(z|x): four stride-2 4x4 convs 50 -> 25 -> 12 -> 6 -> 2 with
+                                                   BatchNorm2d, Linear(1024, 512) + Dropout(0.1), Linear(512, 2D)
+    ImageDecoder     multimnist/model.py:114-142   p(x|z): Linear(D, 1024), transposed convs 2 -> 6 -> 12 -> 25 -> 50
+                                                   (the third is 5x5), logits
+    TextEncoder      multimnist/model.py:145-181   q(z|y): Embedding -> bidirectional GRU -> last position,
                                                    directions summed -> Linear(200, 2D) -> (mu, logvar)
-    TextDecoder      multimnist/model.py:182-228   p(y|z): 4 greedy autoregressive steps of a 2-layer GRU
-    swish / Swish    multimnist/model.py:247-253
-    ProductOfExperts multimnist/model.py:231-244 (the single-eps variant, as celeba's), prior_expert :256-270
+    TextDecoder      multimnist/model.py:184-235   p(y|z): 4 greedy autoregressive steps of a 2-layer GRU
+    swish / Swish    multimnist/model.py:255-261
+    ProductOfExperts multimnist/model.py:238-252 (the single-eps variant, as celeba's), prior_expert :264-277
     max_length, n_characters, SOS, FILL            multimnist/utils.py:12-19
 
-Every matrix product is an ``mvae_linear_*`` launch (leading dimensions make the reference's ``torch.cat((c_in, z))``
-/ ``torch.cat((c_out, z))`` column ranges of one buffer), the gate arithmetic / embeddings / arg-max feedback are the
-K16 kernels of csrc/gru.hip; forward and backward are hand-written (``torch.autograd.Function`` shells), no ATen
-arithmetic.  What the reference evaluates but never uses is not evaluated: the backward direction of the encoder's
-GRU contributes only its FIRST step (on the last character) to ``x[-1]`` (:173).
-
-The rest of ``multimnist/model.py`` -- the 50x50 image stacks (a 5x5 and two pad-0 stride-2 convolutions) and the
-``MVAE`` that joins them -- is outside SURVEY.md section 8 (section 2: ``multimnist/`` is not on the hot path)."""
+The image stacks are ``Stack``s of ``layers.py``: four of their eight convolutions are geometries of the 4x4 kernel
+family (csrc/conv.hip); the odd 25x25 map, the two pad-0 layers and the 5x5 transposed conv run on the general
+stride-2 family (csrc/conv_gen.hip) -- ``layers.py`` picks per launch.  In the text stacks every matrix product is an
+``mvae_linear_*`` launch (leading dimensions make the reference's ``torch.cat((c_in, z))`` / ``torch.cat((c_out, z))``
+column ranges of one buffer), the gate arithmetic / embeddings / arg-max feedback are the K16 kernels of csrc/gru.hip;
+forward and backward are hand-written (``torch.autograd.Function`` shells), no ATen arithmetic.  What the reference
+evaluates but never uses is not evaluated: the backward direction of the encoder's GRU contributes only its FIRST
+step (on the last character) to ``x[-1]`` (:177).  The latent path (PoE, draw, KL) is the fused ``mvae_poe_*`` launch of
+the other four models.  There is no fused or captured MultiMNIST step: ``train.py`` runs the modules eagerly."""
 import warnings
 
 import torch
 import torch.nn as nn
 
 from .. import kernels as K
+from .. import layers as L
+from ..base import MVAEBase, Stack
 from ..base import ProductOfExpertsB as ProductOfExperts, prior_expert  # noqa: F401
 from ..layers import Swish  # noqa: F401
 
@@ -160,13 +168,17 @@ class TextEncoder(nn.Module):
         self.n_hiddens = n_hiddens
         self.bidirectional = bidirectional
 
-    def forward(self, x):
+    def heads(self, x):
+        """The [batch, 2D] output of ``h2p`` (mu | logvar), as the fused PoE launch takes it."""
         _need_gpu(x, 'text'); _need_gpu(self.embed.weight, 'the module')
         if x.dim() != 2 or x.dtype != torch.int64:
             raise ValueError('text must be an int64 [batch, length] tensor of character indices')
         params = _cell_params(self.gru, 0) + (_cell_params(self.gru, 0, True) if self.bidirectional else ())
-        p = _TextEncoderFn.apply(x.contiguous(), self.bidirectional, self.embed.weight, self.h2p.weight, self.h2p.bias,
-                                 *params)
+        return _TextEncoderFn.apply(x.contiguous(), self.bidirectional, self.embed.weight, self.h2p.weight, self.h2p.bias,
+                                    *params)
+
+    def forward(self, x):
+        p = self.heads(x)
         return p[:, :self.n_latents], p[:, self.n_latents:]
 
 
@@ -296,3 +308,115 @@ class TextDecoder(nn.Module):
                                      self.h2o.weight, self.h2o.bias, *(_cell_params(self.gru, 0) + _cell_params(self.gru, 1)))
         self.last_fed = holder.get('fed')
         return words
+
+
+# ----------------------------------------------------------------------------- image stacks
+class ImageEncoder(Stack):
+    """Parametrizes q(z|x) (multimnist/model.py:75-111).  ``dropout_mask`` ([batch, 512] in {0, 1}) replays a host draw of
+    the classifier's Dropout(0.1) in parity runs; otherwise the training-mode mask comes from the device Philox stream."""
+    def __init__(self, n_latents):
+        super().__init__()
+        self.features = nn.Sequential(
+            L.Conv2d(1, 32, 4, 2, 1, bias=False), L.Swish(),
+            L.Conv2d(32, 64, 4, 2, 1, bias=False), L.BatchNorm2d(64), L.Swish(),
+            L.Conv2d(64, 128, 4, 2, 1, bias=False), L.BatchNorm2d(128), L.Swish(),
+            L.Conv2d(128, 256, 4, 2, 0, bias=False), L.BatchNorm2d(256), L.Swish())
+        self.classifier = nn.Sequential(
+            L.Linear(256 * 2 * 2, 512), L.Swish(), L.Dropout(p=0.1), L.Linear(512, n_latents * 2))
+        self.n_latents = n_latents
+
+    def stack_modules(self):
+        return [self.features, L.View(256 * 2 * 2), self.classifier]
+
+    def heads(self, x, dropout_mask=None):
+        masks = None
+        if self.training:
+            if dropout_mask is None:
+                owner = self.__dict__.get('_owner')
+                if owner is None:
+                    raise RuntimeError('encoder is not attached to an MVAE (needed for device-side dropout noise); '
+                                       'pass dropout_mask explicitly')
+                dropout_mask = owner.device_bernoulli(0.9, x.shape[0], 512)
+            masks = [dropout_mask.contiguous().float()]
+        return self.run(x, masks=masks)
+
+    def forward(self, x, dropout_mask=None):
+        h = self.heads(x, dropout_mask)
+        return h[:, :self.n_latents], h[:, self.n_latents:]
+
+
+class ImageDecoder(Stack):
+    """Parametrizes p(x|z) (multimnist/model.py:114-142): [batch, 1, 50, 50] logits."""
+    def __init__(self, n_latents):
+        super().__init__()
+        self.upsample = nn.Sequential(L.Linear(n_latents, 256 * 2 * 2), L.Swish())
+        self.hallucinate = nn.Sequential(
+            L.ConvTranspose2d(256, 128, 4, 2, 0, bias=False), L.BatchNorm2d(128), L.Swish(),
+            L.ConvTranspose2d(128, 64, 4, 2, 1, bias=False), L.BatchNorm2d(64), L.Swish(),
+            L.ConvTranspose2d(64, 32, 5, 2, 1, bias=False), L.BatchNorm2d(32), L.Swish(),
+            L.ConvTranspose2d(32, 1, 4, 2, 1, bias=False))
+
+    def stack_modules(self):
+        return [self.upsample, L.View(256, 2, 2), self.hallucinate]
+
+    def forward(self, z):
+        return self.run(z)  # NOTE: logits, no sigmoid
+
+
+# ----------------------------------------------------------------------------- the model
+class MVAE(MVAEBase):
+    """multimnist/model.py:21-72.  ``forward(image=None, text=None)`` -> (img_recon, txt_recon, mu, logvar); the
+    keyword-only ``eps`` ([batch, D]), ``dropout_mask`` ([batch, 512]) and ``text_dropout_masks`` (4 x [batch, 200])
+    replay host draws in parity runs -- without them the noise comes from the device Philox streams."""
+    POE_VARIANT = 'B'
+    KIND = 'multimnist'
+    LABEL_KIND = 'text'
+    HAS_BN = True
+    IMAGE_SHAPE = (1, 50, 50)
+
+    def __init__(self, n_latents):
+        super().__init__(n_latents)
+        self.image_encoder = ImageEncoder(n_latents)
+        self.image_decoder = ImageDecoder(n_latents)
+        self.text_encoder = TextEncoder(n_latents, n_characters, n_hiddens=200, bidirectional=True)
+        self.text_decoder = TextDecoder(n_latents, n_characters, n_hiddens=200)
+        self.image_encoder.__dict__['_owner'] = self
+
+    def arena_order(self):
+        return [self.image_decoder, self.text_decoder, self.text_encoder, self.image_encoder]
+
+    def text_grad_range(self):
+        """Arena range of the text stacks' parameters.  Their gradients arrive through autograd (the image stacks'
+        kernels write theirs into the arena themselves): ``attach_text_grads`` points those parameters' ``.grad`` at
+        the gradient arena, cleared, so that the arena-wide Adam launch finds every gradient in place."""
+        ranges = self.finalize().module_ranges
+        (a0, a1), (b0, b1) = ranges[self.text_decoder], ranges[self.text_encoder]
+        return min(a0, b0), max(a1, b1)
+
+    def attach_text_grads(self):
+        arena = self.finalize()
+        lo, hi = self.text_grad_range()
+        K.fill_(arena.grad[lo:hi], 0.0)
+        for mod in (self.text_decoder, self.text_encoder):
+            for p in mod.parameters():
+                p.grad = arena.grad_view(p)
+
+    def forward(self, image=None, text=None, *, eps=None, dropout_mask=None, text_dropout_masks=None):
+        mu, logvar, z = self._infer(image, text, eps, dropout_mask, want_z=True)
+        self.__dict__['last_z'] = z.detach()        # the reference does not return the draw; parity runs read it here
+        return self.image_decoder(z), self.text_decoder(z, dropout_masks=text_dropout_masks), mu, logvar
+
+    def infer(self, image=None, text=None):
+        mu, logvar, _ = self._infer(image, text, None, None, want_z=False)
+        return mu, logvar
+
+    def _infer(self, image, text, eps, dropout_mask, want_z):
+        self.finalize()
+        heads = []
+        if image is not None:
+            heads.append(self.image_encoder.heads(image, dropout_mask))
+        if text is not None:
+            heads.append(self.text_encoder.heads(text))
+        if not heads:
+            raise ValueError('at least one modality is required')
+        return self._fuse(heads, eps, want_z)

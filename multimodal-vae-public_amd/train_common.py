@@ -61,8 +61,8 @@ _CELEBA = dict(n_latents=(100, '100'), epochs=(100, '100'), annealing=(20, '20')
 
 
 def _reference_flags(kind):
-    d = _SMALL if kind in ('mnist', 'fashionmnist') else _CELEBA
-    label = 'text' if kind in ('mnist', 'fashionmnist') else 'attrs'
+    d = _SMALL if kind in ('mnist', 'fashionmnist', 'multimnist') else _CELEBA      # multimnist/train.py:144-161
+    label = 'text' if kind in ('mnist', 'fashionmnist', 'multimnist') else 'attrs'
     label_words = 'text' if label == 'text' else 'attributes'
     flags = [
         ('--n-latents', int, d['n_latents'], None, 'size of the latent embedding'),
