@@ -234,7 +234,7 @@ int mvae_convT2d_k4_fwd_stats(const float *x, const float *w, float *part, size_
 #define MVAE_ROUTE_IGEMM            1   /* igemm_kernel on gathered operands (+ split finish for weight gradients) */
 #define MVAE_ROUTE_IGEMM_PAIR       2   /* ... stride-2 dgrad form storing the two column classes of a row as pairs */
 #define MVAE_ROUTE_GEMM2            3   /* gemm2_kernel (forward form; tuning builds only by default) */
-#define MVAE_ROUTE_CONV_PATCH       4   /* conv_patch_kernel (forward form; built in with -DMVAE_CONV_PATCH=1 only) */
+#define MVAE_ROUTE_CONV_PATCH       4   /* retired (the forward-form LDS-patch kernel, removed): never returned; the number stays reserved */
 #define MVAE_ROUTE_SMALL_FWD16      5   /* conv_small_fwd_kernel<Cin, 16>: <= 4 input channels, < 1024 blocks of 32 */
 #define MVAE_ROUTE_SMALL_FWD32      6   /* conv_small_fwd_kernel<Cin, 32> */
 #define MVAE_ROUTE_DGRAD_SMALL3D    7   /* convT_small3d_kernel: <= 4 output channels, rows through LDS by DMA */

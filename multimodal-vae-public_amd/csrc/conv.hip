@@ -4,21 +4,11 @@
 #include "gemm2.h"
 #include "convt_patch.h"
 #include "wgrad_patch.h"
-#include "conv_patch.h"
 
-// k-tile depth of the gather-fed forward / dgrad forms (32 or 64; the weight-gradient loaders decode their
-// tap fields for 32)
+// k-tile depth of the gather-fed forward / dgrad forms (the weight-gradient loaders decode their tap fields for 32)
+constexpr int CONV_BK = 32;
 #ifndef MVAE_SC_BLOCKS
 #define MVAE_SC_BLOCKS 256      // blocks (8 waves each) of the small-Cin conv weight gradient: one per CU
-#endif
-#ifndef MVAE_CONV_SMALL_FWD
-#define MVAE_CONV_SMALL_FWD 1   // <= 4-input-channel stride-2 conv forward: direct VALU kernel instead of a K <= 48 GEMM
-#endif
-#ifndef MVAE_CONVT_SMALL2
-#define MVAE_CONVT_SMALL2 1     // <= 4-channel transposed conv: two positions per thread, weights through scalar loads
-#endif
-#ifndef MVAE_CLS_MINOR
-#define MVAE_CLS_MINOR 1        // parity classes of one tile adjacent in launch order (see igemm_kernel)
 #endif
 #ifndef MVAE_MULTI_ITEMS
 #define MVAE_MULTI_ITEMS 4      // (class, j tile) items a block of the conv forward / dgrad forms walks (1: off)
@@ -26,47 +16,13 @@
 #ifndef MVAE_MULTI_MAXK
 #define MVAE_MULTI_MAXK 256     // ... when the reduction is at most this long (measured: K = 512 tiles lose 2-3 %)
 #endif
-#ifndef MVAE_CONV_BK
-#define MVAE_CONV_BK 32
-#endif
-#ifndef MVAE_FAST_DIV
-#define MVAE_FAST_DIV 1         // shifts instead of run-time divisions in the tile set-up / epilogue of power-of-two layers (0: A/B)
-#endif
-// XCD-aware launch-order re-mapping (round 4; each 0 = plain launch order, for A/B builds)
-#ifndef MVAE_CONV_XCD
-#define MVAE_CONV_XCD 1         // forward / dgrad forms: the channel bands of one column tile on one XCD (igemm_kernel, mode 3)
-#endif
-#ifndef MVAE_WGRAD_XCD
-#define MVAE_WGRAD_XCD 1        // weight-gradient form: the tiles of one k range on one XCD (igemm_kernel, mode 4)
-#endif
-#ifndef MVAE_DY_KEEP
-#define MVAE_DY_KEEP 1          // 32-row transposed-conv form: the column decode of a tile kept across its parity classes (0: A/B)
-#endif
-#ifndef MVAE_SMALL_EPI_BATCH
-#define MVAE_SMALL_EPI_BATCH 1      // conv_small_fwd_kernel: the producer's pre-activations fetched eight channels at a time
-#endif
-#ifndef MVAE_CONVT_SMALL3
-#define MVAE_CONVT_SMALL3 1         // <= 4-output-channel transposed conv: input rows staged through LDS (convT_small3_kernel)
-#endif
 #ifndef MVAE_SMALL2_DEPTH
 #define MVAE_SMALL2_DEPTH 8
-#endif
-#ifndef MVAE_S1_XCD
-#define MVAE_S1_XCD 1           // convT_s1_kernel: the channel groups of one image group on one XCD
 #endif
 
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 __device__ f32x2_t llvm_raw_buffer_load_f32x2(i32x4_t rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v2f32");
 
-#ifndef MVAE_WIDE_BLOCKS
-#define MVAE_WIDE_BLOCKS (1 << 30)   // conv-forward-form launches with >= 128 output channels took 128 x 64 tiles from 384 blocks on
-                                     // (rounds 2-4).  With the gather loaders' one-offset-per-tap form and the buffer-store epilogue
-                                     // the 64 x 64 kernels run four blocks of ~100 registers per CU and WIN: CelebA -1.6 %,
-                                     // FashionMNIST -5.1 %, CelebA-19 -0.7 % (x3 interleaved, profiles/r05_conv_retune_ab.txt); 384: A/B
-#endif
-#ifndef MVAE_GATHER_COMPACT
-#define MVAE_GATHER_COMPACT 1    // gather loaders: one per-lane offset per TAP + the channel on the scalar offset (see LdIm2colT)
-#endif
 
 namespace {
 
@@ -102,7 +58,7 @@ __device__ __forceinline__ void divmod_fast(int m, int d, int lg, int &q, int &r
 // against 1024 MFMA cycles.)
 
 // im2col of x for the forward conv: element (k = (ci,kh,kw), m = (b,oh,ow)); lanes along m.
-template <int TILE_, int BKV_ = MVAE_CONV_BK>
+template <int TILE_, int BKV_ = CONV_BK>
 struct LdIm2colT {
     static constexpr int TILE = TILE_, BKV = BKV_;
     static constexpr int NV = TILE * BKV / NTHREADS;  // elements per thread
@@ -110,12 +66,12 @@ struct LdIm2colT {
     struct Regs { float v[NV]; unsigned ok; };        // raw data + validity bits (applied when staged)
     const float *x; ConvGeom g; int Mtot;
     int base, kq; unsigned vh, vwq;
-    // full k-tiles: buffer base (first image of the tile) + byte offsets.  MVAE_GATHER_COMPACT: an element's offset is
+    // full k-tiles: buffer base (first image of the tile) + byte offsets.  An element's offset is
     // (tap part, per lane) + (channel part, the same for every lane), and its validity depends on the tap alone -- so a
     // thread keeps ONE offset per distinct tap among its elements (4 - 8 instead of 16, out-of-range when the tap is outside
     // the image) and the channel part rides the instruction's SCALAR offset: per (re-)initialisation a handful of vector
     // instructions instead of ~6 per element, and 8 - 12 registers fewer (the multi-item blocks re-initialise per item)
-    BufBase blk; int voff[MVAE_GATHER_COMPACT ? 16 : NV];
+    BufBase blk; int voff[16];
     static constexpr bool fast = true;
     __device__ void begin(int, int) {}
     __device__ void init(int tile0, int t, int) {
@@ -143,20 +99,10 @@ struct LdIm2colT {
         vwq = vw >> kq;
         // element v of a full k-tile: channel (KSTEP*v >> 4) of the tile's channel group, tap (kh, kw); a tap
         // outside the image (or a lane without an output position) reads as zero through BUF_OOB
-        if (MVAE_GATHER_COMPACT) {
 #pragma unroll
-            for (int p = 0; p < 16; ++p) {          // tap (kh, kwl) = (p >> 2, p & 3); the taps no element has are dead code
-                const bool ok = ((vh >> (p >> 2)) & 1u) && ((vwq >> (p & 3)) & 1u);
-                voff[p] = ok ? (rel + (p >> 2) * g.W + (p & 3)) * 4 : BUF_OOB;
-            }
-            return;
-        }
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            const int c = KSTEP * v;
-            const int kwl = c & 3, kh = (c >> 2) & 3, cil = c >> 4;
-            const bool ok = ((vh >> kh) & 1u) && ((vwq >> kwl) & 1u);
-            voff[v] = ok ? (rel + cil * hw + kh * g.W + kwl) * 4 : BUF_OOB;
+        for (int p = 0; p < 16; ++p) {              // tap (kh, kwl) = (p >> 2, p & 3); the taps no element has are dead code
+            const bool ok = ((vh >> (p >> 2)) & 1u) && ((vwq >> (p & 3)) & 1u);
+            voff[p] = ok ? (rel + (p >> 2) * g.W + (p & 3)) * 4 : BUF_OOB;
         }
     }
     __device__ void load(int k0, int kend, int t, Regs &rg) const {
@@ -198,12 +144,8 @@ struct LdIm2colT {
 #pragma unroll
         for (int v = 0; v < NV; ++v)
             if (MVAE_IN_PART(v, NV, part, nparts)) {
-                if (MVAE_GATHER_COMPACT) {
-                    const int c = KSTEP * v;        // tap = c & 15, channel of the tile's group = c >> 4 (scalar offset)
-                    rg.v[v] = llvm_raw_buffer_load_f32(rs, voff[c & 15], (c >> 4) * hw4, 0);
-                } else {
-                    rg.v[v] = buf_load1(rs, voff[v]);
-                }
+                const int c = KSTEP * v;            // tap = c & 15, channel of the tile's group = c >> 4 (scalar offset)
+                rg.v[v] = llvm_raw_buffer_load_f32(rs, voff[c & 15], (c >> 4) * hw4, 0);
             }
     }
     __device__ __forceinline__ void store_part(Tile L, int t, const Regs &rg, int part, int nparts) const {
@@ -253,123 +195,16 @@ struct G2Im2col {
     }
 };
 
-// The same gather staged ROW-major -- LDS image [m][k], k contiguous.  A thread owns one output position m
-// and whole 4-k groups: k = (ci, kh, kw) with kw fastest, so a group is the 4 horizontal taps of one (ci, kh)
-// -- 4 adjacent input floats -- and goes to LDS as ONE float4.  Fragments are then ds_read_b128 (4 MFMAs per
-// read) like the weight operand's.  With the k-major image every MFMA of every wave cost two 256-byte
-// ds_read_b32; at 16 waves per CU (64x64 tiles, one 32x32 accumulator per wave) that alone kept the LDS
-// port ~75 % busy and held the conv kernels near 50 % of the MFMA rate.
-template <int TILE_, int BKV_ = MVAE_CONV_BK>
-struct LdIm2colR {
-    static constexpr int TILE = TILE_, BKV = BKV_;
-    static constexpr int GPT = NTHREADS / TILE;       // thread slots along the 4-k groups
-    static constexpr int NG = BKV / 4;                // 4-k groups per k-tile
-    static constexpr int NV4 = NG / GPT;              // groups per thread
-    static_assert(NG % GPT == 0 && NV4 >= 1, "tile / k-depth combination not covered");
-    struct Regs { float4 v[NV4]; unsigned ok; };      // raw data + 4 validity bits per group
-    const float *x; ConvGeom g; int Mtot;
-    int base, gq; unsigned vh, vw;
-    BufBase blk; int voff[NV4][4];                    // full k-tiles: buffer base (first image of the tile) + byte offsets
-    __device__ void init(int tile0, int t, int) {
-        const int m = tile0 + (t % TILE);
-        gq = t / TILE;
-        vh = 0; vw = 0; base = 0;
-        const int ohw = g.OH * g.OW, hw = g.H * g.W;
-        const int n0 = tile0 / ohw;                   // block-uniform
-        blk = buf_base(x + (size_t)n0 * g.Cin * hw);
-        int rel = 0;
-        if (m < Mtot) {
-            const int b = m / ohw, rem = m - b * ohw;
-            const int oh = rem / g.OW, ow = rem - oh * g.OW;
-            const int ih0 = oh * g.stride - g.pad, iw0 = ow * g.stride - g.pad;
-            base = (b * g.Cin * g.H + ih0) * g.W + iw0;
-            rel = ((b - n0) * g.Cin * g.H + ih0) * g.W + iw0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (ih0 + q >= 0 && ih0 + q < g.H) vh |= 1u << q;
-                if (iw0 + q >= 0 && iw0 + q < g.W) vw |= 1u << q;
-            }
-        }
-#pragma unroll
-        for (int v = 0; v < NV4; ++v) {
-            const int gk = gq + GPT * v, kh = gk & 3, cil = gk >> 2;
-#pragma unroll
-            for (int kw = 0; kw < 4; ++kw) {
-                const bool ok = ((vh >> kh) & 1u) && ((vw >> kw) & 1u);
-                voff[v][kw] = ok ? (rel + cil * hw + kh * g.W + kw) * 4 : BUF_OOB;
-            }
-        }
-    }
-    __device__ void load(int k0, int kend, int t, Regs &rg) const {
-        const int hw = g.H * g.W;
-        const float *src = x + base + (k0 >> 4) * hw;
-        const int safe = (int)(x - src);              // offset of x[0]: always a legal address
-        const int grem = (kend - k0) >> 2;            // groups of this tile inside the reduction (K % 16 == 0)
-        unsigned okbits = 0;
-#pragma unroll
-        for (int v = 0; v < NV4; ++v) {
-            const int gk = gq + GPT * v;              // group = (ci_local, kh)
-            const int kh = gk & 3, cil = gk >> 2;
-            const bool okg = gk < grem && ((vh >> kh) & 1u);
-            const int off = cil * hw + kh * g.W;
-            float e[4];
-#pragma unroll
-            for (int kw = 0; kw < 4; ++kw) {
-                const bool ok = okg && ((vw >> kw) & 1u);
-                e[kw] = src[ok ? off + kw : safe];
-                okbits |= (ok ? 1u : 0u) << (4 * v + kw);
-            }
-            rg.v[v] = make_float4(e[0], e[1], e[2], e[3]);
-        }
-        rg.ok = okbits;
-    }
-    static constexpr bool RMAJOR = true, PARTS = true, TAIL = false, fast = true;
-    __device__ void begin(int, int) {}
-    __device__ __forceinline__ void load_part(int k0, int, int, Regs &rg, int part, int nparts) const {
-        const i32x4_t rs = buf_rsrc(blk, (size_t)(k0 >> 4) * (g.H * g.W));
-#pragma unroll
-        for (int v = 0; v < NV4; ++v)
-            if (MVAE_IN_PART(v, NV4, part, nparts))
-                rg.v[v] = make_float4(buf_load1(rs, voff[v][0]), buf_load1(rs, voff[v][1]), buf_load1(rs, voff[v][2]),
-                                      buf_load1(rs, voff[v][3]));
-    }
-    __device__ __forceinline__ void store_part(float (*L)[BKV_ + LPAD], int t, const Regs &rg, int part, int nparts) const {
-        const int m = t % TILE;
-#pragma unroll
-        for (int v = 0; v < NV4; ++v)
-            if (MVAE_IN_PART(v, NV4, part, nparts)) *reinterpret_cast<float4 *>(&L[m][4 * (gq + GPT * v)]) = rg.v[v];
-    }
-    static constexpr int ROWS = TILE, PITCH = BKV + LPAD;
-    typedef float (*Tile)[PITCH];
-    static __device__ __forceinline__ float4 frag(Tile L, int k0, int row) {
-        return *reinterpret_cast<const float4 *>(&L[row][k0]);
-    }
-    __device__ void store(Tile L, int t, const Regs &rg) const {
-        const int m = t % TILE;
-#pragma unroll
-        for (int v = 0; v < NV4; ++v) {
-            const unsigned b = rg.ok >> (4 * v);
-            *reinterpret_cast<float4 *>(&L[m][4 * (gq + GPT * v)]) =
-                make_float4(rg.v[v].x * mask0(b & 1u), rg.v[v].y * mask0(b & 2u), rg.v[v].z * mask0(b & 4u),
-                            rg.v[v].w * mask0(b & 8u));
-        }
-    }
-};
-#ifndef MVAE_GATHER_ROWMAJOR
-#define MVAE_GATHER_ROWMAJOR 0      // measured (r2): no gain over the k-major image, see DESIGN.md
-#endif
-#if MVAE_GATHER_ROWMAJOR
-template <int T> using LdIm2col = LdIm2colR<T>;
-#else
+// (The same gather staged ROW-major -- LDS image [m][k], one float4 per 4-k group, ds_read_b128 fragments -- measured no gain
+//  over the k-major image in round 2, see DESIGN.md: retired.)
 template <int T> using LdIm2col = LdIm2colT<T>;
-#endif
 
 
 // Transposed-conv (dgrad) gather of dy for the output parity class `cls` = (ph,pw) of dx:
 // element (k = (co,a,b), m = (n, ih', iw')) with ih = ih'*s + ph, kh = kh0 + s*a,
 // oh = (ih + pad - kh0)/s - a.  TPD = 4/s taps per dim (TLOG = log2 TPD); only the taps that can
 // reach the class are enumerated, so stride 2 does no multiply-by-zero work.
-template <int TILE_, int TLOG, int BKV_ = MVAE_CONV_BK>
+template <int TILE_, int TLOG, int BKV_ = CONV_BK>
 struct LdDgradDyT {
     static constexpr int TILE = TILE_, BKV = BKV_;
     static constexpr bool PAIRABLE = (TLOG == 1);     // stride 2: classes = the 2 x 2 output parities (EpNCHW pair stores)
@@ -380,14 +215,14 @@ struct LdDgradDyT {
     const float *dy; ConvGeom g; int Mtot; int H2, W2;
     int base, kq; unsigned vhq, vwq;
     static constexpr int NPAT = (TMASK + 1) * (TMASK + 1);      // taps (a, b) per class
-    BufBase blk; int voff[MVAE_GATHER_COMPACT ? NPAT : NV];     // full k-tiles: buffer base (first image of the tile) + byte offsets (see LdIm2colT)
+    BufBase blk; int voff[NPAT];      // full k-tiles: buffer base (first image of the tile) + byte offsets (see LdIm2colT)
     // The column -> (image, row', col') decode of a tile (two run-time divisions per thread) is the same for every
     // parity class of that tile, and a multi-item block walks the classes of ONE tile back to back (class-minor
     // order): kept across init() calls.  The (stride, pad) pair is the template's: 4x4 convs here are (2, 1) or (1, 0).
     // Only the 32-row layout (128-column tiles, 8 k-steps per item) keeps it: there the set-up is as long as the loop;
     // the 64-row kernels sit at 127 registers and the three extra ones would cost them an occupancy step.
     static constexpr int S = (TLOG == 1) ? 2 : 1, PD = (TLOG == 1) ? 1 : 0;
-    static constexpr bool KEEP = (TILE_ == 128) && MVAE_DY_KEEP;
+    static constexpr bool KEEP = (TILE_ == 128);
     int c_tile0 = -1, c_n = 0, c_n0 = 0, c_ih2 = 0, c_iw2 = 0;
     static constexpr bool fast = true;
     __device__ void begin(int, int) {}
@@ -424,20 +259,10 @@ struct LdDgradDyT {
             }
         }
         vhq = vh >> aq; vwq = vw >> bq;
-        if (MVAE_GATHER_COMPACT) {
 #pragma unroll
-            for (int p = 0; p < NPAT; ++p) {        // tap (al, bl) = (p >> TLOG, p & TMASK)
-                const bool ok = ((vhq >> (p >> TLOG)) & 1u) && ((vwq >> (p & TMASK)) & 1u);
-                voff[p] = ok ? (rel - (p >> TLOG) * g.OW - (p & TMASK)) * 4 : BUF_OOB;
-            }
-            return;
-        }
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            const int c = KSTEP * v;
-            const int bl = c & TMASK, al = (c >> TLOG) & TMASK, col = c >> (2 * TLOG);
-            const bool ok = ((vhq >> al) & 1u) && ((vwq >> bl) & 1u);
-            voff[v] = ok ? (rel + col * ohw - al * g.OW - bl) * 4 : BUF_OOB;
+        for (int p = 0; p < NPAT; ++p) {            // tap (al, bl) = (p >> TLOG, p & TMASK)
+            const bool ok = ((vhq >> (p >> TLOG)) & 1u) && ((vwq >> (p & TMASK)) & 1u);
+            voff[p] = ok ? (rel - (p >> TLOG) * g.OW - (p & TMASK)) * 4 : BUF_OOB;
         }
     }
     __device__ void load(int k0, int kend, int t, Regs &rg) const {
@@ -478,12 +303,8 @@ struct LdDgradDyT {
 #pragma unroll
         for (int v = 0; v < NV; ++v)
             if (MVAE_IN_PART(v, NV, part, nparts)) {
-                if (MVAE_GATHER_COMPACT) {
-                    const int c = KSTEP * v;        // tap = low 2 TLOG bits, output channel of the tile's group above them
-                    rg.v[v] = llvm_raw_buffer_load_f32(rs, voff[c & (NPAT - 1)], (c >> (2 * TLOG)) * ohw4, 0);
-                } else {
-                    rg.v[v] = buf_load1(rs, voff[v]);
-                }
+                const int c = KSTEP * v;            // tap = low 2 TLOG bits, output channel of the tile's group above them
+                rg.v[v] = llvm_raw_buffer_load_f32(rs, voff[c & (NPAT - 1)], (c >> (2 * TLOG)) * ohw4, 0);
             }
     }
     __device__ __forceinline__ void store_part(Tile L, int t, const Regs &rg, int part, int nparts) const {
@@ -493,122 +314,13 @@ struct LdDgradDyT {
             if (MVAE_IN_PART(v, NV, part, nparts)) L[kb + v * KSTEP][m] = rg.v[v];
     }
 };
-// Row-major staging of the same gather (see LdIm2colR): a 4-k group is the 2x2 taps of one output channel
-// (stride 2) or the 4 horizontal taps of one (channel, vertical tap) (stride 1).
-template <int TILE_, int TLOG, int BKV_ = MVAE_CONV_BK>
-struct LdDgradDyR {
-    static constexpr int TILE = TILE_, BKV = BKV_;
-    static constexpr int GPT = NTHREADS / TILE;
-    static constexpr int NG = BKV / 4;
-    static constexpr int NV4 = NG / GPT;
-    static_assert(NG % GPT == 0 && NV4 >= 1, "tile / k-depth combination not covered");
-    struct Regs { float4 v[NV4]; unsigned ok; };
-    const float *dy; ConvGeom g; int Mtot; int H2, W2;
-    int base, gq; unsigned vh, vw;
-    BufBase blk; int voff[NV4][4];                    // full k-tiles: buffer base (first image of the tile) + byte offsets
-    __device__ void init(int tile0, int t, int cls) {
-        const int ph = cls / g.stride, pw = cls % g.stride;
-        const int kh0 = (ph + g.pad) % g.stride, kw0 = (pw + g.pad) % g.stride;
-        const int m = tile0 + (t % TILE);
-        gq = t / TILE;
-        vh = 0; vw = 0; base = 0;
-        const int hw2 = H2 * W2, ohw = g.OH * g.OW;
-        const int n0 = tile0 / hw2;                   // block-uniform
-        blk = buf_base(dy + (size_t)n0 * g.Cout * ohw);
-        int rel = 0;
-        if (m < Mtot) {
-            const int n = m / hw2, rem = m - n * hw2;
-            const int ih2 = rem / W2, iw2 = rem - ih2 * W2;
-            const int ohb = (ih2 * g.stride + ph + g.pad - kh0) / g.stride;
-            const int owb = (iw2 * g.stride + pw + g.pad - kw0) / g.stride;
-            base = (n * g.Cout * g.OH + ohb) * g.OW + owb;
-            rel = ((n - n0) * g.Cout * g.OH + ohb) * g.OW + owb;
-#pragma unroll
-            for (int a = 0; a < (1 << TLOG); ++a) {
-                if (ohb - a >= 0 && ohb - a < g.OH) vh |= 1u << a;
-                if (owb - a >= 0 && owb - a < g.OW) vw |= 1u << a;
-            }
-        }
-#pragma unroll
-        for (int v = 0; v < NV4; ++v) {
-            const int gk = gq + GPT * v;
-            const int col = TLOG == 1 ? gk : gk >> 2, a_g = TLOG == 1 ? 0 : gk & 3;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int a = TLOG == 1 ? (q >> 1) : a_g, b = TLOG == 1 ? (q & 1) : q;
-                const bool ok = ((vh >> a) & 1u) && ((vw >> b) & 1u);
-                voff[v][q] = ok ? (rel + col * ohw - a * g.OW - b) * 4 : BUF_OOB;
-            }
-        }
-    }
-    __device__ void load(int k0, int kend, int t, Regs &rg) const {
-        const int ohw = g.OH * g.OW;
-        const float *src = dy + base + (k0 >> (2 * TLOG)) * ohw;
-        const int safe = (int)(dy - src);
-        const int grem = (kend - k0) >> 2;
-        unsigned okbits = 0;
-#pragma unroll
-        for (int v = 0; v < NV4; ++v) {
-            const int gk = gq + GPT * v;
-            // stride 2 (TLOG 1): group = channel, elements (a, b) = (e >> 1, e & 1);
-            // stride 1 (TLOG 2): group = (channel, a), elements b = e
-            const int col = TLOG == 1 ? gk : gk >> 2, a_g = TLOG == 1 ? 0 : gk & 3;
-            float e[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int a = TLOG == 1 ? (q >> 1) : a_g, b = TLOG == 1 ? (q & 1) : q;
-                const bool ok = gk < grem && ((vh >> a) & 1u) && ((vw >> b) & 1u);
-                e[q] = src[ok ? col * ohw - a * g.OW - b : safe];
-                okbits |= (ok ? 1u : 0u) << (4 * v + q);
-            }
-            rg.v[v] = make_float4(e[0], e[1], e[2], e[3]);
-        }
-        rg.ok = okbits;
-    }
-    static constexpr bool RMAJOR = true, PARTS = true, TAIL = false, fast = true;
-    __device__ void begin(int, int) {}
-    __device__ __forceinline__ void load_part(int k0, int, int, Regs &rg, int part, int nparts) const {
-        const i32x4_t rs = buf_rsrc(blk, (size_t)(k0 >> (2 * TLOG)) * (g.OH * g.OW));
-#pragma unroll
-        for (int v = 0; v < NV4; ++v)
-            if (MVAE_IN_PART(v, NV4, part, nparts))
-                rg.v[v] = make_float4(buf_load1(rs, voff[v][0]), buf_load1(rs, voff[v][1]), buf_load1(rs, voff[v][2]),
-                                      buf_load1(rs, voff[v][3]));
-    }
-    __device__ __forceinline__ void store_part(float (*L)[BKV_ + LPAD], int t, const Regs &rg, int part, int nparts) const {
-        const int m = t % TILE;
-#pragma unroll
-        for (int v = 0; v < NV4; ++v)
-            if (MVAE_IN_PART(v, NV4, part, nparts)) *reinterpret_cast<float4 *>(&L[m][4 * (gq + GPT * v)]) = rg.v[v];
-    }
-    static constexpr int ROWS = TILE, PITCH = BKV + LPAD;
-    typedef float (*Tile)[PITCH];
-    static __device__ __forceinline__ float4 frag(Tile L, int k0, int row) {
-        return *reinterpret_cast<const float4 *>(&L[row][k0]);
-    }
-    __device__ void store(Tile L, int t, const Regs &rg) const {
-        const int m = t % TILE;
-#pragma unroll
-        for (int v = 0; v < NV4; ++v) {
-            const unsigned b = rg.ok >> (4 * v);
-            *reinterpret_cast<float4 *>(&L[m][4 * (gq + GPT * v)]) =
-                make_float4(rg.v[v].x * mask0(b & 1u), rg.v[v].y * mask0(b & 2u), rg.v[v].z * mask0(b & 4u),
-                            rg.v[v].w * mask0(b & 8u));
-        }
-    }
-};
-#if MVAE_GATHER_ROWMAJOR
-template <int TILE_> using LdDgradDyS2 = LdDgradDyR<TILE_, 1>;   // stride 2: 2x2 taps per class
-template <int TILE_> using LdDgradDyS1 = LdDgradDyR<TILE_, 2>;   // stride 1: all 4x4 taps
-#else
 template <int TILE_> using LdDgradDyS2 = LdDgradDyT<TILE_, 1>;   // stride 2: 2x2 taps per class
 template <int TILE_> using LdDgradDyS1 = LdDgradDyT<TILE_, 2>;   // stride 1: all 4x4 taps
-#endif
 // the weight-side loaders of those two forms at the same k-tile depth
-template <int T> using LdRowsKC = LdRowsKT<T, true, MVAE_CONV_BK>;
-template <int T> using LdRowsKSC = LdRowsKT<T, false, MVAE_CONV_BK>;
-template <int T> using LdRowsMNC = LdRowsMNT<T, true, MVAE_CONV_BK>;
-template <int T> using LdRowsMNSC = LdRowsMNT<T, false, MVAE_CONV_BK>;
+template <int T> using LdRowsKC = LdRowsKT<T, true, CONV_BK>;
+template <int T> using LdRowsKSC = LdRowsKT<T, false, CONV_BK>;
+template <int T> using LdRowsMNC = LdRowsMNT<T, true, CONV_BK>;
+template <int T> using LdRowsMNSC = LdRowsMNT<T, false, CONV_BK>;
 
 // wgrad operands: the reduction runs over k = (b,oh,ow); lanes along k (spatially contiguous).
 //
@@ -823,7 +535,6 @@ inline ConvGeom make_geom(int B, int Cin, int H, int W, int Cout, int stride, in
     const int H2 = H / stride, W2 = W / stride;
     g.lg_hw2 = (log2_or_neg(H2) >= 0 && log2_or_neg(W2) >= 0) ? log2_or_neg(H2 * W2) : -1;
     g.lg_w2 = g.lg_hw2 >= 0 ? log2_or_neg(W2) : -1;
-    if (!MVAE_FAST_DIV) g.lg_ohw = g.lg_ow = g.lg_hw2 = g.lg_w2 = -1;
     return g;
 }
 
@@ -900,7 +611,7 @@ __global__ __launch_bounds__(256) void conv_small_fwd_kernel(const float *__rest
     }
     const int ohw = g.OH * g.OW;
     const size_t o0 = ((size_t)n * g.Cout + cg) * ohw + (size_t)oh * g.OW + ow0;
-    if (MVAE_SMALL_EPI_BATCH && dpre && cg + CG <= g.Cout) {
+    if (dpre && cg + CG <= g.Cout) {
         // the data-gradient use (ConvTranspose2d(64, 1) / (32, 3) backward, times the producer's Swish'): the producer's
         // pre-activations of EIGHT channels are fetched together, one batch ahead of the batch being finished.  In the
         // loop below every channel's load sits under its own block-uniform branches, hipcc waits for the whole memory
@@ -952,19 +663,16 @@ __global__ __launch_bounds__(256) void conv_small_fwd_kernel(const float *__rest
 }
 
 inline bool conv_fwd_small_ok(const ConvGeom &g, const float *x, const float *pre, const float *act, const float *dpre) {
-    return MVAE_CONV_SMALL_FWD && g.Cin <= 4 && g.stride == 2 && g.pad == 1 && g.H == 2 * g.OH && g.W == 2 * g.OW &&
+    return g.Cin <= 4 && g.stride == 2 && g.pad == 1 && g.H == 2 * g.OH && g.W == 2 * g.OW &&
            g.OW % 2 == 0 && aligned8(x) && (!pre || aligned8(pre)) && (!act || aligned8(act)) && (!dpre || aligned8(dpre));
 }
 
-#ifndef MVAE_SMALL_FWD_CG16
-#define MVAE_SMALL_FWD_CG16 1     // 16-channel groups for launches with < 1024 blocks of 32 (0: A/B builds)
-#endif
 // A thread carries 64 accumulators and walks CIN * 4 dependent trips of six loads: with two blocks per CU (Conv2d(3, 32) at
 // 256 images: 512 blocks) nothing covers a trip's latency -- 22.9 us re-issued hot, 31.5 us in the step, where x comes
 // from HBM.  Half the channels per thread = twice the blocks.
 inline bool conv_fwd_small_half(const ConvGeom &g) {
     const long total = (long)g.B * g.OH * (g.OW / 2);
-    return MVAE_SMALL_FWD_CG16 && g.Cout % 16 == 0 && ((total + 255) / 256) * ((g.Cout + 31) / 32) < 1024;
+    return g.Cout % 16 == 0 && ((total + 255) / 256) * ((g.Cout + 31) / 32) < 1024;
 }
 
 inline int conv_fwd_small(const float *x, const float *w, float *pre, float *act, const float *dpre, ConvGeom g,
@@ -987,11 +695,11 @@ inline int conv_fwd_small(const float *x, const float *w, float *pre, float *act
 }
 
 // ---- which launch a conv-forward-form call takes (conv_fwd_impl switches on it, mvae_conv_k4_route reports it) ----
-struct ConvFwdRoute { int route; Plan pl; ConvPatchPlan pp; G2Plan g2; };
+struct ConvFwdRoute { int route; Plan pl; G2Plan g2; };
 inline ConvFwdRoute conv_fwd_route(const ConvGeom &g, const float *x, const float *w, const float *pre, const float *act,
                                    const float *dpre, bool launching) {
     ConvFwdRoute r;
-    r.pp.kind = 0; r.g2.ok = false;
+    r.g2.ok = false;
     const int I = g.Cout, J = g.B * g.OH * g.OW, K = g.Cin * 16;
     if (conv_fwd_small_ok(g, x, pre, act, dpre) && !MVAE_TUNE(wm)) {
         r.route = conv_fwd_small_half(g) ? MVAE_ROUTE_SMALL_FWD16 : MVAE_ROUTE_SMALL_FWD32;
@@ -999,19 +707,13 @@ inline ConvFwdRoute conv_fwd_route(const ConvGeom &g, const float *x, const floa
     }
     Plan &pl = r.pl;
     pl = make_plan(I, J, K, false);
-    // >= 128 output channels and enough columns for >= 384 blocks of 128 x 64: two accumulators per wave share
-    // every gathered fragment (dec2 / dec1 dgrad at 512 images: 91 -> 99 and 77 -> 80 TFLOP/s; at 256 images the
-    // grid would be one block per CU and 64 x 64 tiles win)
-    if (pl.wm == 1 && pl.wn == 1 && pl.kw == 1 && pl.wgn == 2 && I >= 128 && !MVAE_TUNE(wm) && !MVAE_TUNE(wn) &&
-        cdiv(I, 128) * cdiv(J, 64) >= MVAE_WIDE_BLOCKS)
-        pl.wm = 2;
+    // (>= 128 output channels took 128 x 64 tiles from 384 blocks on in rounds 2-4.  With the gather loaders' one-offset-per-tap
+    //  form and the buffer-store epilogue the 64 x 64 kernels run four blocks of ~100 registers per CU and win: CelebA -1.6 %,
+    //  FashionMNIST -5.1 %, CelebA-19 -0.7 %, x3 interleaved, profiles/r05_conv_retune_ab.txt)
     if (K <= MVAE_MULTI_MAXK) pl.items = MVAE_MULTI_ITEMS;      // short reductions: pipeline across consecutive tiles
-    pl.xcd = MVAE_CONV_XCD ? 3 : 0;                             // the bands of one column tile on one XCD (igemm_kernel)
-    if (MVAE_CONV_PATCH && aligned16(w) && aligned16(x) && MVAE_EP_BUFFER && !MVAE_TUNE(wm)) {
-        // the input as an LDS patch, the weights as they lie in memory (conv_patch.h)
-        r.pp = conv_patch_plan(g.B, g.Cin, g.H, g.W, g.Cout, g.OH, g.OW, g.stride, g.pad);
-        if (r.pp.kind >= 1 && r.pp.kind <= 4) { r.route = MVAE_ROUTE_CONV_PATCH; return r; }
-    }
+    pl.xcd = 3;                                                 // the bands of one column tile on one XCD (igemm_kernel)
+    // (the input as an LDS patch with the weights as they lie in memory measured equal to 10 % slower than this launch on
+    //  every layer -- profiles/r06_conv_patch_bench.txt -- and is retired: MVAE_ROUTE_CONV_PATCH is never returned)
     if (aligned16(w) && (size_t)g.Cin * g.H * g.W * 4 * (256 / (g.OH * g.OW) + 2) < ((size_t)1 << 31)) {
         void *g2ws = nullptr; size_t g2ws_bytes = 0;
 #ifdef MVAE_TUNING
@@ -1044,10 +746,6 @@ int conv_fwd_impl(const float *x, const float *w, float *pre, float *act, const 
     switch (r.route) {
         case MVAE_ROUTE_SMALL_FWD16: return conv_fwd_small(x, w, pre, act, dpre, g, true, st);
         case MVAE_ROUTE_SMALL_FWD32: return conv_fwd_small(x, w, pre, act, dpre, g, false, st);
-        case MVAE_ROUTE_CONV_PATCH:
-            if (r.pp.kind == 2) return launch_conv_patch<324>(r.pp, x, w, e, st);
-            if (r.pp.kind == 3) return launch_conv_patch<592>(r.pp, x, w, e, st);
-            return launch_conv_patch<260>(r.pp, x, w, e, st);                    // kinds 1 and 4
         case MVAE_ROUTE_GEMM2: return launch_gemm2<G2RowsK, G2Im2col, EpNCHW, false>(r.g2, mp, mq, e, st);
         default: break;
     }
@@ -1352,9 +1050,6 @@ __global__ __launch_bounds__(256) void convT_small3_kernel(const float *__restri
     }
 }
 
-#ifndef MVAE_SMALL3_DMA
-#define MVAE_SMALL3_DMA 1         // convT_small3's staging by LDS-DMA into a 3-deep ring (0: registers + ds_write, A/B builds)
-#endif
 // The same kernel with the zero-bordered channel images filled by LDS-DMA (gemm2.h's machinery): a channel image is NQ pieces of 64
 // consecutive LDS floats, a piece = one `buffer_load_dword ... lds` whose lane l fetches the input element that belongs at float
 // 64 q + l of the image -- or nothing: a border, a row outside the map, an image past the batch or the tail of the padded image is
@@ -1472,7 +1167,7 @@ __global__ __launch_bounds__(256) void convT_small3d_kernel(const float *__restr
 
 // block geometry and batch depth of convT_small3_kernel; false: the shape stays with convT_small2_kernel
 inline bool conv_small3_plan(const ConvGeom &g, Small3Geo &sg, int &depth, size_t &lds) {
-    if (!MVAE_CONVT_SMALL3 || (g.OW & 1) || g.OW / 2 > 256) return false;
+    if ((g.OW & 1) || g.OW / 2 > 256) return false;
     const int OW2 = g.OW / 2;
     sg.R = g.OH < 256 / OW2 ? g.OH : 256 / OW2;
     sg.NI = 256 / (sg.R * OW2);
@@ -1506,7 +1201,7 @@ inline bool conv_small3_dma_plan(const ConvGeom &g, const Small3Geo &sg, int &qp
     const int nq = (sg.ch_stride + 63) / 64;
     qpw = (nq + 3) / 4;
     ldsd = ((size_t)3 * 4 * nq * 64 + 256) * sizeof(float);
-    return MVAE_SMALL3_DMA && g.Cout % 4 == 0 && qpw >= 2 && qpw <= 3 && ldsd <= 48 * 1024;
+    return g.Cout % 4 == 0 && qpw >= 2 && qpw <= 3 && ldsd <= 48 * 1024;
 }
 
 // which of the direct <= 4-channel kernels a launch takes (conv_dgrad_small switches on it)
@@ -1517,7 +1212,7 @@ inline int conv_dgrad_small_route(const ConvGeom &g, const float *dy, const floa
         int qpw; size_t ldsd;
         return conv_small3_dma_plan(g, sg, qpw, ldsd) ? MVAE_ROUTE_DGRAD_SMALL3D : MVAE_ROUTE_DGRAD_SMALL3;
     }
-    if (MVAE_CONVT_SMALL2 && g.OW % 2 == 0 && aligned16(dx ? dx : act) && (!dx || !act || aligned16(act)) && (!dpre || aligned16(dpre)) &&
+    if (g.OW % 2 == 0 && aligned16(dx ? dx : act) && (!dx || !act || aligned16(act)) && (!dpre || aligned16(dpre)) &&
         aligned8(dy))
         return MVAE_ROUTE_DGRAD_SMALL2;
     return MVAE_ROUTE_DGRAD_SMALL;
@@ -1605,43 +1300,27 @@ inline int conv_dgrad_small(int route, const float *dy, const float *w, float *d
 //      fragments; k loop over Cout; the finished 128 x 64 tile is parked in LDS and every thread gathers the
 //      <= 16 taps of its output pixels. ----
 constexpr int S1_ROWS = 128, S1_COLS = 64;
-#ifndef MVAE_S1_BK
-#define MVAE_S1_BK 16           // k-tile depth of convT_s1_kernel: 16 = 33 KB of LDS (the col2im tile), FOUR blocks per CU; 32 = 51 KB, three (round 3).  More co-resident blocks hide the cold prologue + col2im epilogue of each: CelebA-19 6.67 -> 6.55 ms, CelebA 2.453 -> 2.425 (profiles/r04_s1bk_wgt_ab.txt)
-#endif
-constexpr int S1_BK = MVAE_S1_BK;
-#ifndef MVAE_S1_TAPS
-#define MVAE_S1_TAPS 1          // 8x8 outputs: the col2im tap table is computed once per thread, not once per image (0: A/B builds)
-#endif
-#ifndef MVAE_S1_EPI2
-#define MVAE_S1_EPI2 1          // 5 x 5 -> 8 x 8: col2im with a zero slot, a row / column tap table and the image as an immediate (0: A/B builds)
-#endif
-#ifndef MVAE_S1_DMA
-#define MVAE_S1_DMA 1           // operands by LDS-DMA into a 3-deep ring (dy rows as 4-byte pieces, weight rows as 16-byte pieces): no staging
-#endif                          // registers, no ds_write, two k-tiles in flight behind the one being multiplied (0: register staging, A/B builds)
+// k-tile depth (the DMA ring moves four k rows of P and one 16-byte piece of Q per wave: 16, nothing else): 33 KB of LDS (the
+// col2im tile), FOUR blocks per CU; 32 was 51 KB, three (round 3).  More co-resident blocks hide the cold prologue + col2im
+// epilogue of each: CelebA-19 6.67 -> 6.55 ms, CelebA 2.453 -> 2.425 (profiles/r04_s1bk_wgt_ab.txt)
+constexpr int S1_BK = 16;
 #ifndef MVAE_S1_WIDE_MIN
-#define MVAE_S1_WIDE_MIN 6144   // blocks (of 128 columns) from which a launch takes the wide form of convT_s1_kernel; 0: never (A/B builds)
+#define MVAE_S1_WIDE_MIN 6144   // blocks (of 128 columns) from which a launch takes the wide form of convT_s1_kernel; 0: never
 #endif
-#ifndef MVAE_S1_KO
-#define MVAE_S1_KO 0            // knock-out builds (tools/build_variants.sh; results are WRONG by construction): low 3 bits 1 = no global loads in
-#endif                          // the main loop, 2 = + no LDS stores / barriers, 3 = + no fragment reads; bit 3 (8) = no col2im epilogue
-// CW: 64-column blocks (4 channels x 16 taps) per block.  CW = 2 (DMA form only): 128 x 128 block tiles, 64 x 64 per wave -- every
+// CW: 64-column blocks (4 channels x 16 taps) per block.  CW = 2: 128 x 128 block tiles, 64 x 64 per wave -- every
 // fragment read feeds two matrix instructions, a barrier every 32 of them, half the dy pieces per matrix instruction; the col2im
 // runs once per column block through the same 33-KB tile.  48 KB of ring: three blocks per CU.  The host picks it for launches
 // with enough blocks (conv_dgrad_s1).
 template <int CW>
 __global__ __launch_bounds__(256, 2) void convT_s1_kernel(const float *dy, const float *w, float *out, float *act,
                                                           const float *dpre, ConvGeom g, int NI) {
-    static_assert(CW == 1 || (CW == 2 && MVAE_S1_DMA), "the wide form exists on the DMA ring only");
-    constexpr int PP = S1_ROWS + LPAD, QP = S1_COLS + LPAD, TP = S1_COLS + 1;
-    constexpr int P_FL = S1_BK * PP, Q_FL = S1_BK * QP;
+    static_assert(CW == 1 || CW == 2, "narrow or wide form");
+    constexpr int TP = S1_COLS + 1;
     constexpr int COLS = S1_COLS * CW;
     // (col2im in two 32-column passes -- 17 KB of staging, six blocks per CU -- measured neutral against four: not kept)
     constexpr int S1_ST = 3, ST_FL = S1_BK * (S1_ROWS + COLS);          // DMA ring: stages, floats per stage (P [BK][128], then Q [BK][COLS])
-    constexpr int RING_FL = MVAE_S1_DMA ? S1_ST * ST_FL : 2 * P_FL + 2 * Q_FL;
+    constexpr int RING_FL = S1_ST * ST_FL;
     __shared__ __attribute__((aligned(16))) float s1_lds[RING_FL > S1_ROWS * TP ? RING_FL : S1_ROWS * TP];
-    auto Ps = [&](int b2) { return reinterpret_cast<float (*)[PP]>(s1_lds + b2 * P_FL); };
-    auto Qs = [&](int b2) { return reinterpret_cast<float (*)[QP]>(s1_lds + 2 * P_FL + b2 * Q_FL); };
-    (void)Ps; (void)Qs;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wi = wave >> 1, wj = wave & 1;
     const int P = g.OH * g.OW;                      // positions per image (<= 32)
@@ -1653,7 +1332,7 @@ __global__ __launch_bounds__(256, 2) void convT_s1_kernel(const float *dy, const
     // x, x + 8, ... with all their channel groups back to back: dy comes in once, the 2 MB of weights are resident
     // in every L2 (the host pads gridDim.y to a multiple of 8; the padding blocks leave here).
     int by = blockIdx.y, bx = blockIdx.x;
-    if (MVAE_S1_XCD) {
+    {
         const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y, xcd = lin & 7u, slot = lin >> 3;
         const unsigned grp = slot / gridDim.x;
         bx = (int)(slot - grp * gridDim.x);
@@ -1662,7 +1341,6 @@ __global__ __launch_bounds__(256, 2) void convT_s1_kernel(const float *dy, const
     }
     const int n0 = by * NI, ci0 = bx * 4 * CW;
     const int K = g.Cout, J = g.Cin * 16;
-#if MVAE_S1_DMA
     // Operands by LDS-DMA (gemm2.h's machinery).  A stage holds k-tile [k0, k0 + 16): P as [k][128 packed rows] -- the 25
     // positions of an image at one channel are contiguous in dy but start at a multiple of 100 bytes, so its pieces are
     // 4-byte ones: one instruction fills 64 rows of one k (lane = row: image / position / validity are lane constants, the k
@@ -1670,7 +1348,7 @@ __global__ __launch_bounds__(256, 2) void convT_s1_kernel(const float *dy, const
     // -- and Q as [k][64] by 16-byte pieces (a k row of the weight slab = 64 contiguous floats; one instruction = four rows).
     // Per wave and stage: 8 + 1 instructions, no vector registers, no ds_write.  Three stages: while k-tile s is multiplied,
     // s + 1 has landed or is landing and s + 2 is requested -- in the step the dy tile comes from HBM (118 MB at 4608 images:
-    // 1139 us in situ against 991 re-issued hot), and one tile ahead in registers did not cover that.
+    // 1139 us in situ against 991 re-issued hot), and one tile ahead in registers (the round-3 staging) did not cover that.
     static_assert(S1_BK == 16, "four k rows of P and one 16-byte piece of Q per wave");
     const int wv = g2_uni(wave);
     const unsigned lds0 = (unsigned)(unsigned long)(g2_lds_void *)s1_lds;
@@ -1756,93 +1434,6 @@ __global__ __launch_bounds__(256, 2) void convT_s1_kernel(const float *dy, const
         }
     }
     __syncthreads();                                // every wave is done with the ring: the col2im tile takes its place
-#else
-    // P loader: lanes along the packed row axis r = image * P + position, 2 k rows per pass.  Buffer loads
-    // (gemm_core.h): the lane part of the address -- image, position, k parity -- is a constant voffset (BUF_OOB
-    // for the 3 pad rows / images past the batch: zero fill), the k-step part rides the scalar soffset; nothing
-    // on the vector ALU (K % BK == 0 is a launch condition).  (Measured and not kept, round 4: lanes walking the
-    // contiguous S1_BK * P run of each image -- 256 contiguous bytes per wave load instead of ~7 lines -- with the LDS
-    // places as thread constants: 16 more registers, CelebA-19 6.63 -> 6.76 ms, profiles/r04_s1bk_wgt_ab.txt.)
-    const int pr_ = t & 127, pkq = t >> 7;
-    const int pimg = pr_ / P, ppos = pr_ - pimg * P;
-    const bool pok = pimg < NI && n0 + pimg < g.B;
-    const int pvoff = pok ? ((pimg * K + pkq) * P + ppos) * 4 : BUF_OOB;
-    const BufBase pblk = buf_base(dy + (size_t)n0 * K * P);
-    // Q loader: weight rows are contiguous in (ci, tap): 16 float4 per k row, 2 per thread
-    const BufBase qblk = buf_base(w + (size_t)ci0 * 16);
-    constexpr int S1_NP = S1_BK / 2, S1_NQ = S1_BK / 16;    // dwords of dy / float4 of w a thread moves per k-step
-    int qvoff[S1_NQ];
-#pragma unroll
-    for (int v = 0; v < S1_NQ; ++v) {
-        const int f = t + 256 * v;
-        qvoff[v] = ((f >> 4) * J + (f & 15) * 4) * 4;
-    }
-    float pr[S1_NP];
-    float4 qr[S1_NQ];
-    auto load = [&](int k0) {
-        const i32x4_t prs = buf_rsrc(pblk, 0), qrs = buf_rsrc(qblk, (size_t)k0 * J);
-#pragma unroll
-        for (int v = 0; v < S1_NP; ++v) pr[v] = llvm_raw_buffer_load_f32(prs, pvoff, (k0 + 2 * v) * P * 4, 0);
-#pragma unroll
-        for (int v = 0; v < S1_NQ; ++v) qr[v] = buf_load4(qrs, qvoff[v]);
-    };
-    auto store = [&](int buf) {
-#pragma unroll
-        for (int v = 0; v < S1_NP; ++v) Ps(buf)[pkq + 2 * v][pr_] = pr[v];
-#pragma unroll
-        for (int v = 0; v < S1_NQ; ++v) {
-            const int f = t + 256 * v;
-            *reinterpret_cast<float4 *>(&Qs(buf)[f >> 4][(f & 15) * 4]) = qr[v];
-        }
-    };
-    f32x16 acc[1][2];
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[0][x][r] = 0.f;
-    const int lrow = lane >> 5, lcol = lane & 31;
-    const int nsteps = (K + S1_BK - 1) / S1_BK;
-    load(0);
-    store(0);
-    __syncthreads();
-    for (int s = 0; s < nsteps; ++s) {
-        const int buf = s & 1;
-        if ((MVAE_S1_KO & 7) < 1) load(min(s + 1, nsteps - 1) * S1_BK);    // unconditional (the last trip re-reads its own tile): no branch
-        float a0[2], b0;
-        a0[0] = Ps(buf)[lrow][wi * 64 + lcol]; a0[1] = Ps(buf)[lrow][wi * 64 + 32 + lcol];
-        b0 = Qs(buf)[lrow][wj * 32 + lcol];
-#pragma unroll
-        for (int kk = 0; kk < S1_BK / 2; ++kk) {
-            float a1[2] = {0.f, 0.f}, b1 = 0.f;
-            if ((MVAE_S1_KO & 7) >= 3) { a1[0] = a0[0]; a1[1] = a0[1]; b1 = b0; }
-            else if (kk + 1 < S1_BK / 2) {
-                a1[0] = Ps(buf)[(kk + 1) * 2 + lrow][wi * 64 + lcol];
-                a1[1] = Ps(buf)[(kk + 1) * 2 + lrow][wi * 64 + 32 + lcol];
-                b1 = Qs(buf)[(kk + 1) * 2 + lrow][wj * 32 + lcol];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[0], b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[1], b0, acc[0][1], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            a0[0] = a1[0]; a0[1] = a1[1]; b0 = b1;
-        }
-        if ((MVAE_S1_KO & 7) < 2) {
-            store(buf ^ 1);
-            __syncthreads();
-        }
-    }
-#endif
-    if (MVAE_S1_KO & 8) {           // no col2im: one (never taken) store keeps the matrix instructions alive
-        float sum = 0.f;
-#pragma unroll
-        for (int y = 0; y < CW; ++y)
-#pragma unroll
-            for (int x = 0; x < 2; ++x)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sum += acc[y][x][r];
-        if (sum == 12345.678f && out) out[t] = sum;
-        return;
-    }
     auto col2im = [&](const f32x16 (&accy)[2], const int cib) {
         // col2im: park the 128 (packed positions) x 64 (4 channels x 16 taps) tile in LDS and let every thread gather the
         // <= 16 taps of its output pixels (image, channel, pixel).  The reads are unconditional from clamped positions with
@@ -1855,11 +1446,11 @@ __global__ __launch_bounds__(256, 2) void convT_s1_kernel(const float *dy, const
                 const int row = wi * 64 + x * 32 + (r & 3) + 8 * (r >> 2) + 4 * lrow;
                 sc[row * TP + wj * 32 + lcol] = accy[x][r];
             }
-        if (MVAE_S1_EPI2 && t < 5) sc[t * 25 * TP + S1_COLS] = 0.f;     // the pad column of the first row of each 5 x 5 image: the zero its taps outside the image read
+        if (t < 5) sc[t * 25 * TP + S1_COLS] = 0.f;     // the pad column of the first row of each 5 x 5 image: the zero its taps outside the image read
         __syncthreads();
         const int HW = g.H * g.W;
         const int per_img = 4 * HW;
-        if (MVAE_S1_EPI2 && g.H == 8 && g.W == 8 && g.OH == 5 && g.OW == 5) {
+        if (g.H == 8 && g.W == 8 && g.OH == 5 && g.OW == 5) {
             // 5 x 5 -> 8 x 8 (the two layers this kernel serves), NI = 5 whole images: as the path below, with what was still
             // re-derived per image or per tap taken out (profiles/r06_celeba_sq_counters.txt: 3.7 vector instructions per matrix
             // instruction over this kernel, 0.9 in its main loop -- the rest is here).  A tap outside the image reads the zero
@@ -1897,7 +1488,7 @@ __global__ __launch_bounds__(256, 2) void convT_s1_kernel(const float *dy, const
             }
             return;
         }
-        if (MVAE_S1_TAPS && g.H == 8 && g.W == 8) {
+        if (g.H == 8 && g.W == 8) {
             // 8 x 8 outputs (both layers that use this kernel): 4 channels x 64 pixels = the 256 threads, so a thread's
             // (channel, pixel) -- and with it the 16 tap positions and their validity -- is the same for every image of the
             // block: computed ONCE; per image a tap is one address add, one LDS read, one FMA.  On fp32 MFMA the vector
@@ -1979,38 +1570,29 @@ inline bool conv_dgrad_s1_ok(const ConvGeom &g, const float *w) {
 inline dim3 conv_dgrad_s1_grid(const ConvGeom &g) {
     const int NI = S1_ROWS / (g.OH * g.OW);         // whole images per block
     dim3 grid(g.Cin / 4, (g.B + NI - 1) / NI);
-    if (MVAE_S1_XCD) grid.y = (grid.y + 7) / 8 * 8;   // XCD-local image groups (see the kernel)
+    grid.y = (grid.y + 7) / 8 * 8;                  // XCD-local image groups (see the kernel)
     return grid;
 }
 // 128-column blocks (three per CU) where the launch still has MVAE_S1_WIDE_MIN of them: the 4608-image passes of celeba19
 inline bool conv_dgrad_s1_wide(const ConvGeom &g) {
-#if MVAE_S1_DMA
     return MVAE_S1_WIDE_MIN > 0 && g.Cin % 8 == 0 && (long)(g.Cin / 8) * conv_dgrad_s1_grid(g).y >= MVAE_S1_WIDE_MIN;
-#else
-    return false;
-#endif
 }
 
 inline int conv_dgrad_s1(bool wide, const float *dy, const float *w, float *dx, float *act, const float *dpre, ConvGeom g,
                          hipStream_t st) {
     const int NI = S1_ROWS / (g.OH * g.OW);
     dim3 grid = conv_dgrad_s1_grid(g);
-#if MVAE_S1_DMA
     if (wide) {
         grid.x = g.Cin / 8;
         hipLaunchKernelGGL(convT_s1_kernel<2>, grid, dim3(256), 0, st, dy, w, dx, act, dpre, g, NI);
         return mvae_launch_status();
     }
-#endif
     hipLaunchKernelGGL(convT_s1_kernel<1>, grid, dim3(256), 0, st, dy, w, dx, act, dpre, g, NI);
     return mvae_launch_status();
 }
 
 inline size_t dgrad_ws_floats(const ConvGeom &g) { return (size_t)g.Cout * g.Cin * 16; }
 
-#ifndef MVAE_PAIR_STORE
-#define MVAE_PAIR_STORE 1
-#endif
 #ifndef MVAE_PAIR_MAXK
 #define MVAE_PAIR_MAXK 512
 #endif
@@ -2033,13 +1615,13 @@ inline ConvDgradRoute conv_dgrad_route(const ConvGeom &g, const float *dy, const
     Plan &pl = r.pl;
     pl = make_plan(I, J, K, false, PLAN_FWD, s * s);
     if (K <= MVAE_MULTI_MAXK) pl.items = MVAE_MULTI_ITEMS;      // short reductions: pipeline across consecutive tiles / classes
-    pl.xcd = MVAE_CONV_XCD ? 3 : 0;
+    pl.xcd = 3;
     r.vec = (g.Cin % 4 == 0) && aligned16(wr);
     // pair stores (gemm_core.h EpNCHW::PAIR): class-minor item order puts (py, 0), (py, 1) back to back in a block
-    r.pair = (MVAE_PAIR_STORE && s == 2 && MVAE_CLS_MINOR && g.W % 2 == 0 && (!dx || aligned8(dx)) && (!act || aligned8(act)) &&
+    r.pair = (s == 2 && g.W % 2 == 0 && (!dx || aligned8(dx)) && (!act || aligned8(act)) &&
               (!dpre || aligned8(dpre))) ? 1 : 0;
     r.route = MVAE_ROUTE_IGEMM;
-    if (r.vec && s == 2 && r.pair && MVAE_EP_BUFFER && !MVAE_TUNE(wm) && aligned16(dy)) {
+    if (r.vec && s == 2 && r.pair && !MVAE_TUNE(wm) && aligned16(dy)) {
         // one LDS input patch for the four parity classes (convt_patch.h): the 64- and 32-row layers on 7 x 7 / 8 x 8 / 16 x 16 maps
         r.pp = convt_patch_plan(g.B, g.Cout, g.Cin, g.OH, g.OW, false);
         if (r.pp.kind == 1) { r.route = MVAE_ROUTE_PATCH8; return r; }
@@ -2100,7 +1682,7 @@ int conv_dgrad_impl(const float *dy, const float *w, float *dx, float *act, cons
     auto mq = [&](auto &q) { q.dy = dy; q.g = g; q.Mtot = J; q.H2 = H2; q.W2 = W2; };
     SplitSink sink = make_sink(nullptr, I, J, false);
     sink.ncls = s * s;      // all parity classes in ONE launch: s*s times the blocks
-    sink.cls_minor = MVAE_CLS_MINOR;
+    sink.cls_minor = 1;     // the parity classes of one tile adjacent in launch order (see igemm_kernel)
     switch (r.route) {
         case MVAE_ROUTE_PATCH8: return launch_convt_patch2<EpNCHWPair, 1, 68, true, MVAE_PATCH_STAGE8 ? 8 : 0, 8>(r.pp, dy, wr, ep, st);
         case MVAE_ROUTE_PATCH7: return launch_convt_patch2<EpNCHWPair, 1, 148, false, MVAE_PATCH_STAGE7 ? 7 : 0, 11>(r.pp, dy, wr, ep, st);
@@ -2128,7 +1710,7 @@ inline long conv_dgrad_stats_tiles(const ConvGeom &g) {
     if (s != 2 || g.pad != 1 || g.Cin > 32 || g.Cin % 4 != 0) return 0;
     const long J = (long)g.B * (g.H / s) * (g.W / s);
     const int K = g.Cout << 2;
-    if (J % STATS_TILE != 0 || K % MVAE_CONV_BK != 0 || K < 2 * MVAE_CONV_BK || J * 4 >= (1L << 31)) return 0;
+    if (J % STATS_TILE != 0 || K % CONV_BK != 0 || K < 2 * CONV_BK || J * 4 >= (1L << 31)) return 0;
     return J / STATS_TILE;
 }
 
@@ -2492,9 +2074,6 @@ __global__ __launch_bounds__(1024) void finish_wide_kernel(SplitSink sink, int s
     }
 }
 
-#ifndef MVAE_SC2
-#define MVAE_SC2 1                // weight gradient of the <= 4-input-channel convs: the LDS-DMA kernel (0: the register-staged one)
-#endif
 #ifndef MVAE_SC2_STAGES
 #define MVAE_SC2_STAGES 2
 #endif
@@ -2512,7 +2091,6 @@ inline int wgrad_smallcin_blocks(const ConvGeom &g) {
 // the LDS-DMA kernel's launch geometry; false: no instantiation for this layer (the register-staged kernel runs it)
 struct Sc2Geo { int xw, p; size_t lds; };
 inline bool wgrad_smallcin2_plan(const ConvGeom &g, Sc2Geo &q) {
-    if (!MVAE_SC2) return false;
     const int I = g.Cout, J = g.Cin * 16;
     const int mt = I / 32, nt = (J + 31) / 32;
     q.xw = g.W + 8;
@@ -2553,7 +2131,7 @@ inline ConvWgradRoute conv_wgrad_route(const ConvGeom &g, const float *dy, const
         }
     }
     r.pl = make_plan(I, J, K, true, PLAN_CONV_WGRAD);
-    r.pl.xcd = MVAE_WGRAD_XCD ? 4 : 0;                          // the tiles of one k range on one XCD (igemm_kernel)
+    r.pl.xcd = 4;                                               // the tiles of one k range on one XCD (igemm_kernel)
     r.route = MVAE_ROUTE_IGEMM;
     r.splits = r.pl.splits;
     if (r.pl.splits > 1 && (!ws || ws_bytes < r.pl.splits * make_sink(ws, I, J, false).stride * sizeof(float))) r.route = MVAE_ERR_WS;
@@ -2614,7 +2192,7 @@ int conv_wgrad_impl(const float *dy, const float *x, float *dw, ConvGeom g, int 
 #undef MVAE_SC
         }
         SplitSink fs = make_sink(ws, I, J, false);
-        if (blocks > 16 && blocks <= 1024 && MVAE_SC2) {
+        if (blocks > 16 && blocks <= 1024) {
             hipLaunchKernelGGL((finish_wide_kernel<EpRowMajor>), dim3((J + 31) / 32, I), dim3(1024), 0, st, fs, blocks, e);
         } else if (blocks > 16) {
             hipLaunchKernelGGL((finish_kernel<EpRowMajor>), dim3((J + 31) / 32, I), dim3(256), 0, st, fs, blocks, e);

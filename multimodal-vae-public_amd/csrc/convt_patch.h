@@ -29,17 +29,11 @@
 
 namespace {
 
-#ifndef MVAE_CONVT_PATCH
-#define MVAE_CONVT_PATCH 1          // 0: every stride-2 dgrad-form launch stays on igemm_kernel (A/B builds)
-#endif
 #ifndef MVAE_PATCH_STAGE7
 #define MVAE_PATCH_STAGE7 0         // 1: 7 x 7 lattices: outputs through LDS, whole lines per store.  Measured x3 interleaved (profiles/r06_patch_ab.txt): FashionMNIST 2.1103 ms against 2.0945 with pair stores (2.1032 on the gather launch) -- not the partial lines: off
 #endif
 #ifndef MVAE_PATCH_STAGE8
 #define MVAE_PATCH_STAGE8 0         // 8 x 8 lattices: the same (64-byte output rows)
-#endif
-#ifndef MVAE_PATCH_CONSTGEO
-#define MVAE_PATCH_CONSTGEO 1       // the lattice of an instantiation as compile-time constants (0: run-time divisors, A/B builds)
 #endif
 #ifndef MVAE_PATCH_MINBLK
 #define MVAE_PATCH_MINBLK 4         // blocks per CU the register allocation aims at: the LDS footprint (40 KB) admits four; at 2 the
@@ -75,11 +69,7 @@ __global__ __launch_bounds__(256, MVAE_PATCH_MINBLK) void convT_patch2_kernel(co
     // the lattice this instantiation serves (convt_patch_plan picks it by exactly these geometries): every division of the
     // per-tile set-up below is by a constant -- shifts for the 8 x 8 / 16 x 16 maps.  With run-time divisors the set-up was 249
     // vector instructions per wave and tile (656 on the 7 x 7 maps) against 256 matrix instructions of a 64 -> 32-channel tile.
-#if MVAE_PATCH_CONSTGEO
     constexpr int W2c = PS == 68 ? 8 : PS == 100 ? 16 : 7, H2c = W2c, OHWc = W2c * W2c;
-#else
-    const int W2c = g.W2, H2c = g.H2, OHWc = g.OHW;
-#endif
     constexpr bool STATS = ep_stats<E>::value;
     constexpr int PSV = X4 ? PS / 4 : PS;
     constexpr int PATCH_FLOATS = NUI * 256 * (X4 ? 4 : 1);  // one buffer
@@ -326,7 +316,6 @@ __global__ __launch_bounds__(256, MVAE_PATCH_MINBLK) void convT_patch2_kernel(co
 struct PatchPlan { int kind; PatchGeo g; int blocks; size_t lds; };
 inline PatchPlan convt_patch_plan(int B, int Cout, int Cin, int OH, int OW, bool stats) {
     PatchPlan pl; pl.kind = 0;
-    if (!MVAE_CONVT_PATCH) return pl;
 #ifdef MVAE_TUNING
     if (getenv("MVAE_PATCH_OFF")) return pl;
 #endif

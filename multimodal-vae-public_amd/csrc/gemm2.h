@@ -420,13 +420,6 @@ __global__ __launch_bounds__(256) void g2_finish_kernel(E e, G2Args a) {
 // ---- host side
 struct G2Plan { int wm, wn, occ, stages; bool ok; size_t ws_floats; G2Args a; };
 
-#ifndef MVAE_G2_ACT_ONLY
-#define MVAE_G2_ACT_ONLY 1        // 0: A/B builds
-#endif
-#ifndef MVAE_G2
-#define MVAE_G2 1                 // 0: every launch stays on the round-1-5 kernels (A/B builds)
-#endif
-
 // tile shape by a cost model: a block's time is its k-tiles x the MFMAs of a k-tile, and a launch lasts as long as the
 // busiest CU; larger tiles read less per flop (LDS fragments, L2 -> LDS bytes) and pay more for ragged edges and slabs
 inline G2Plan g2_plan(int I, int J, int K, int ncls, bool rowsum, int force_wm = 0, int force_wn = 0, int force_occ = 0) {
@@ -485,7 +478,6 @@ inline G2Plan g2_plan(int I, int J, int K, int ncls, bool rowsum, int force_wm =
 enum G2Hint { G2_PLAIN = 0, G2_FWD_TWO_OUTPUTS = 1, G2_CONV_FWD = 2, G2_FWD_ACT_ONLY = 3 };
 inline G2Plan g2_plan_for(int I, int J, int K, int ncls, bool rowsum, void *ws, size_t ws_bytes, G2Hint hint = G2_PLAIN) {
     G2Plan none; none.ok = false;
-    if (!MVAE_G2) return none;
     int fwm = 0, fwn = 0, focc = 0;
 #ifdef MVAE_TUNING
     if (getenv("MVAE_G2_OFF")) return none;
@@ -493,10 +485,10 @@ inline G2Plan g2_plan_for(int I, int J, int K, int ncls, bool rowsum, void *ws, 
 #endif
     if (!fwm) {
         const long tiles64 = cdiv(I, 64) * cdiv(J, 64) * ncls;
-        // ... and (MVAE_G2_ACT_ONLY) the forwards of a statistics-only pass, which keep the Swish output alone, over a very short
+        // ... and the forwards of a statistics-only pass, which keep the Swish output alone, over a very short
         // reduction: celeba19's 4608 x 6400 x 100 (7200 tiles of four k-steps: prologue and epilogue are the launch)
         const bool two = hint == G2_FWD_TWO_OUTPUTS && K <= 640 && tiles64 >= 1536;
-        const bool one = MVAE_G2_ACT_ONLY && hint == G2_FWD_ACT_ONLY && K <= 128 && tiles64 >= 1536;
+        const bool one = hint == G2_FWD_ACT_ONLY && K <= 128 && tiles64 >= 1536;
         if (!two && !one) return none;
         fwm = 1; fwn = 1; focc = -1;
     }
@@ -718,9 +710,6 @@ void gemm2s_kernel(const float *__restrict__ P, int ldp, size_t p_cs, const floa
     }
 }
 
-#ifndef MVAE_G2S
-#define MVAE_G2S 1                // 0: the k-grouped small layouts of gemm_core.h everywhere (A/B builds)
-#endif
 #ifndef MVAE_G2S_STAGES
 #define MVAE_G2S_STAGES 4
 #endif
@@ -729,7 +718,7 @@ void gemm2s_kernel(const float *__restrict__ P, int ldp, size_t p_cs, const floa
 template <class E, bool Q_RK>
 bool launch_gemm2s(const Plan &pl, const float *P, int ldp, size_t p_cs, const float *Q, int ldq, size_t q_cs, E e, int I,
                    int J, int K, int ncls, hipStream_t st, int *status) {
-    if (!MVAE_G2S || pl.bk != 64 || pl.splits != 1 || (K & 3)) return false;
+    if (pl.bk != 64 || pl.splits != 1 || (K & 3)) return false;
 #ifdef MVAE_TUNING
     if (getenv("MVAE_G2S_OFF")) return false;
 #endif

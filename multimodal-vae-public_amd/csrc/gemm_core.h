@@ -37,91 +37,24 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// Tuning overrides exist only in the -DMVAE_TUNING build (libmvae_hip_tuning.so, used by tools/gemm_bench.py);
-// the product library has no mutable global state: MVAE_TUNE(x) folds to 0.
-#ifndef MVAE_STAGGER
-#define MVAE_STAGGER 0          // > 0: s_sleep units (64 cycles) per CU slot at kernel start (experiment)
-#endif
-#ifndef MVAE_INTERLEAVE
-#define MVAE_INTERLEAVE 1       // 1: next-tile loads / stores sliced into the MFMA groups' shadows (see igemm_kernel)
-#endif
-#ifndef MVAE_KO_EPI
-#define MVAE_KO_EPI 0           // knock-out experiment (results are wrong): 1 = the conv / Linear epilogues store nothing
-#endif
-// ... unless the value equals this constant, i.e. never -- but the test keeps the accumulators (and with them every MFMA) alive:
-// with an unconditional return the compiler deleted the matrix instructions and the build "ran at the matrix floor" (SQ_INSTS_MFMA = 0)
-#define MVAE_KO_MAGIC 1.2345678e-31f
-#ifndef MVAE_KO
-#define MVAE_KO 0               // knock-out experiments on the interleaved loop (results are wrong): 1 no global loads,
-#endif                          // 2 + no LDS stores, 3 + no barrier, 4 + no fragment reads (MFMAs only)
-#ifndef MVAE_PAIR_NEIGH
-#define MVAE_PAIR_NEIGH 1       // pair-storing transposed-conv launches: the two class PAIRS of a j tile on neighbouring blocks of one XCD
-                                // (2 items per block) instead of four consecutive items of one block: the second pair re-reads the
-                                // tile's input microseconds -- not ~45 us -- after the first, and the 128-byte output lines the pairs
-                                // share meet in the L2.  profiles/r05_convT_class_ab.txt (x2 interleaved, outputs identical to the last
-                                // digit): FashionMNIST's dominant launch -2.8 %, its step -0.5 / -0.7 %, CelebA-19 -0.2 %, CelebA -0.1 ... -0.4 %.
-                                // (Non-temporal stores for the output, measured beside it, LOSE: that launch +4 %.)  0: A/B
-#endif
+// sizing parameters (overridable: tools/build_variants.sh)
 #ifndef MVAE_MULTI_MINBLOCKS
 #define MVAE_MULTI_MINBLOCKS 1024   // a multi-item launch keeps at least this many column blocks (4 per CU)
 #endif
 #ifndef MVAE_WGRAD_TARGET
-#define MVAE_WGRAD_TARGET 512   // blocks a split conv weight gradient aims for (two per CU); fewer = fewer partial slabs (A/B builds)
+#define MVAE_WGRAD_TARGET 512   // blocks a split conv weight gradient aims for (two per CU); fewer = fewer partial slabs
 #endif
 #ifndef MVAE_WGRAD_TILE
 #define MVAE_WGRAD_TILE 128
 #endif
-#ifndef MVAE_XCD_ROWS
-#define MVAE_XCD_ROWS 0         // 1: Linear launches map XCDs to ROW BANDS of the output (experiment; see igemm_kernel)
-#endif
-#ifndef MVAE_SETPRIO
-#define MVAE_SETPRIO 0          // 1: raise the wave priority around each MFMA group (measured: see DESIGN.md)
-#endif
+// Tuning overrides exist only in the -DMVAE_TUNING build (libmvae_hip_tuning.so, used by tools/gemm_bench.py);
+// the product library has no mutable global state: MVAE_TUNE(x) folds to 0.
 #ifdef MVAE_TUNING
 struct MvaeTune { int wm, wn, splits, kw, small_off, small_waves; long split_target; int knockout; };
 extern MvaeTune g_mvae_tune;      // defined in linear.hip
 #define MVAE_TUNE(f) (g_mvae_tune.f)
 #else
 #define MVAE_TUNE(f) 0
-#endif
-#ifndef MVAE_FINISH_PREFETCH
-#define MVAE_FINISH_PREFETCH 0
-#endif
-#ifndef MVAE_PHASED_PRELOAD
-#define MVAE_PHASED_PRELOAD 2    // k-grouped blocks, two tiles really in flight (see the phased loop): 1 = every wave issues the tile loads
-                                 // (out of range for the MFMA-only waves), 2 = those waves run a load-free copy of the loop, 0 = rounds 1-4.
-                                 // Round 4 measured 1 once (+2.4 %) and never ran 2.  Round 5, x3 interleaved on one box
-                                 // (profiles/r05_mnist_switches_ab.txt): 0: 0.2874 / 0.2897 / 0.2854 ms, 1: 0.2918 / 0.2928 / 0.2896,
-                                 // 2: 0.2780 / 0.2837 / 0.2837 -- the movers' copy has no control-flow merge between its loads and its
-                                 // stores, the compiler's wait counts are the two-tiles-in-flight ones, and the MFMA-only waves issue
-                                 // no dummy loads: MNIST -2 %; 111 parity tests green on that build.  Adopted.
-#endif
-#ifndef MVAE_PHASED_DEPTH
-#define MVAE_PHASED_DEPTH 2      // register sets (k-tiles in flight) of the movers in the k-grouped layouts' loop: 2, or 4 (A/B).  FOUR
-                                 // tiles in flight make the launch itself faster (MNIST's 1024 x 512 x 512: 13.2 -> 12.4 us by rocprof,
-                                 // single stream) and the STEP 9 % slower (0.3067-0.3077 vs 0.2808-0.2812 ms, x3 interleaved,
-                                 // profiles/r05_mnist_switches_ab.txt): the movers then hold 171 registers, a 512-thread block fills
-                                 // half of every SIMD's register file, and the two chain kernels the step's two streams run side
-                                 // by side no longer share a CU.  Two tiles: 116-122 registers, two blocks per CU.
-#endif
-#ifndef MVAE_CHAIN_PRIO
-#define MVAE_CHAIN_PRIO 0        // 1-3: the k-grouped (small-layout) GEMMs -- the launches of MNIST's data-gradient chains -- raise their
-                                 // wave priority for their whole run.  Measured x3 (profiles/r05_wgrad_ab.txt): nothing -- beside a
-                                 // weight-gradient batch the two launches share the MFMA pipes whatever their priority.  Off.
-#endif
-#ifndef MVAE_EP_BUFFER
-#define MVAE_EP_BUFFER 1         // NCHW tile epilogues through buffer stores: per-lane column offset + SCALAR row offset, no 64-bit
-                                 // address arithmetic per element (0: the round-4 pointer form)
-#endif
-#ifndef MVAE_EPI_BATCH
-#define MVAE_EPI_BATCH 0         // tile epilogues: the operands of eight outputs fetched together.  Off: with 3-5 blocks per CU the other
-                                 // blocks' matrix work already covers a block's epilogue -- CelebA +0.6 %, FashionMNIST +0.1 % (r04_epilogue_ab.txt)
-#endif
-#ifndef MVAE_EPI_PREFETCH_ROWRED
-#define MVAE_EPI_PREFETCH_ROWRED 1     // ... also for the loss-folding epilogues (bias, target / label, row coefficient)
-#endif
-#ifndef MVAE_EPI_PREFETCH
-#define MVAE_EPI_PREFETCH 1      // small layouts: the epilogue's operands fetched ahead of the main loop (0: rounds 1-3)
 #endif
 
 // raw buffer loads, declared on the LLVM intrinsics (see "buffer loads for the main loops" below)
@@ -211,11 +144,7 @@ struct LdRowsKT {
     BufBase blk;                                      //              address of (row r0, k = 0)
     static constexpr bool fast = true;
     __device__ void begin(int, int) {}
-    // a thread that fetches nothing (the MFMA-only waves of a k-grouped block): every buffer load reads out of range
-    __device__ void disable() {
-#pragma unroll
-        for (int v = 0; v < (VEC ? NV : 1); ++v) voff[v] = BUF_OOB;
-    }
+    static constexpr bool MOVERS_LOOP = true;         // k-grouped blocks: the movers run their own copy of the phased loop
     __device__ void init(int tile0, int t, int cls) {
         r0 = tile0; cls_off = (size_t)cls * cls_stride;
         if (VEC) {
@@ -313,11 +242,7 @@ struct LdRowsMNT {
     BufBase blk;                                      //              address of (k = 0, r0)
     static constexpr bool fast = true;
     __device__ void begin(int, int) {}
-    // a thread that fetches nothing (the MFMA-only waves of a k-grouped block): every buffer load reads out of range
-    __device__ void disable() {
-#pragma unroll
-        for (int v = 0; v < (VEC ? NV : 1); ++v) voff[v] = BUF_OOB;
-    }
+    static constexpr bool MOVERS_LOOP = true;         // k-grouped blocks: the movers run their own copy of the phased loop
     __device__ void init(int tile0, int t, int cls) {
         r0 = tile0; cls_off = (size_t)cls * cls_stride;
         if (VEC) {
@@ -413,7 +338,6 @@ struct EpRowMajor {
     }
     __device__ bool col(int j) const { return j < J; }
     __device__ void put(int i, int j, float v) const {
-        if (MVAE_KO_EPI && v != MVAE_KO_MAGIC) return;
         if (i >= I) return;
         if (bias) v += bias[j];
         float m = 1.f;
@@ -442,7 +366,6 @@ struct EpRowMajor {
         return p;
     }
     __device__ void put_pre(int i, int j, float v, const Pre &p) const {
-        if (MVAE_KO_EPI && v != MVAE_KO_MAGIC) return;
         if (i >= I) return;
         if (bias) v += p.b;
         float m = 1.f;
@@ -454,9 +377,8 @@ struct EpRowMajor {
         if (act) act[idx] = swishf_(v) * m;
     }
 };
-template <class T, class = void> struct ld_can_disable : std::false_type {};
-template <class T> struct ld_can_disable<T, std::void_t<decltype(std::declval<T &>().disable())>> : std::true_type {};
-template <bool ON, class L> __device__ __forceinline__ void loader_disable(L &l) { if constexpr (ON) l.disable(); }
+template <class T, class = void> struct ld_movers_loop : std::false_type {};
+template <class T> struct ld_movers_loop<T, std::void_t<decltype(T::MOVERS_LOOP)>> : std::integral_constant<bool, T::MOVERS_LOOP> {};
 template <class T, class = void> struct ep_prefetch : std::false_type {};
 template <class T> struct ep_prefetch<T, std::void_t<decltype(T::PREFETCH)>> : std::integral_constant<bool, T::PREFETCH> {};
 template <class T, bool = ep_prefetch<T>::value> struct ep_pre { struct type {}; };
@@ -600,7 +522,7 @@ struct EpNCHW {
     int pair = 0;                             // host-side choice between the two types
     __device__ bool pair_ok() const { return pair != 0; }
     __device__ void put2(int i, float v0, float v1) const {      // off was computed for px = 0
-        if ((MVAE_KO_EPI && !(v0 == MVAE_KO_MAGIC && v1 == MVAE_KO_MAGIC)) || i >= C) return;
+        if (i >= C) return;
         const int idx = off + i * HW;
         if (dpre) {
             const float2 d = *reinterpret_cast<const float2 *>(dpre + idx);
@@ -635,7 +557,7 @@ struct EpNCHW {
         return true;
     }
     __device__ void put(int i, int, float v) const {
-        if ((MVAE_KO_EPI && v != MVAE_KO_MAGIC) || i >= C) return;
+        if (i >= C) return;
         const int idx = off + i * HW;
         if (dpre) v *= swish_grad_(dpre[idx]);
         if (out) out[idx] = v;
@@ -647,7 +569,7 @@ struct EpNCHW {
     //      and on fp32 MFMA a vector instruction is matrix time).  Here an access is  descriptor(tile's first image) +
     //      per-lane byte offset (col(), once per column) + SCALAR row offset: no vector arithmetic at all.  A lane without
     //      a column carries BUF_OOB: its loads read 0, its stores are dropped -- no divergent branch around the tile either.
-    static constexpr bool BUFFER = MVAE_EP_BUFFER != 0;
+    static constexpr bool BUFFER = true;
     int n0 = 0, voff = 0;
     i32x4_t r_out, r_act, r_dpre;
     __device__ void tile(int j0) {          // j0: the tile's first column (block-uniform)
@@ -661,7 +583,6 @@ struct EpNCHW {
     }
     // rb: first row of the wave's 32-row fragment (wave-uniform); r: accumulator register 0 .. 15
     __device__ __forceinline__ void put_b(int rb, int r, float v) const {
-        if (MVAE_KO_EPI && v != MVAE_KO_MAGIC) return;
         const int is = rb + (r & 3) + 8 * (r >> 2);             // row of the LOWER half wavefront
         int vo = voff;
         if (C & 7) {                                            // block-uniform; channel counts here are multiples of 8
@@ -675,7 +596,6 @@ struct EpNCHW {
         if (act) llvm_raw_buffer_store_f32(swishf_(v), r_act, vo, so, 0);
     }
     __device__ __forceinline__ void put2_b(int rb, int r, float v0, float v1) const {      // col() ran for px = 0
-        if (MVAE_KO_EPI && !(v0 == MVAE_KO_MAGIC && v1 == MVAE_KO_MAGIC)) return;
         const int is = rb + (r & 3) + 8 * (r >> 2);
         int vo = voff;
         if (C & 7) {
@@ -797,7 +717,6 @@ void igemm_kernel(P p, Q q, E e, int K, int klen, SplitSink sink) {
     auto Ps = [&](int b) { return reinterpret_cast<PTile>(lds_raw + b * P_FLOATS); };
     auto Qs = [&](int b) { return reinterpret_cast<QTile>(lds_raw + 2 * P_FLOATS + b * Q_FLOATS); };
 
-    if (MVAE_CHAIN_PRIO && KW > 1 && WGM * WGN < 4) __builtin_amdgcn_s_setprio(MVAE_CHAIN_PRIO);
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int kg = wave / WPG, wq = wave % WPG;     // k-group of this wave, its slot inside the group
     const int wi = wq / WGN, wj = wq % WGN;
@@ -810,8 +729,11 @@ void igemm_kernel(P p, Q q, E e, int K, int klen, SplitSink sink) {
         // fabric for 5 MB of operands).  Re-map the launch order so that XCD x owns a (tiles_i / 4) x (tiles_j / 2)
         // sub-grid of the output: P is fetched by 2 XCDs, Q by 4 (host checks divisibility, one class, no split).
         const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), xcd = lin & 7u, slot = lin >> 3;
-        if (MVAE_PAIR_NEIGH && sink.xcd_map == 5) {
-            // experiment: XCD x owns j tiles x, x + 8, ...; the two class pairs of a tile sit in consecutive slots
+        if (sink.xcd_map == 5) {
+            // pair-storing transposed-conv launches: XCD x owns j tiles x, x + 8, ...; the two class PAIRS of a tile sit in consecutive
+            // slots (2 items per block), so the second pair re-reads the tile's input microseconds after the first and the 128-byte
+            // output lines the pairs share meet in the L2: FashionMNIST's dominant launch -2.8 %, its step -0.5 / -0.7 %
+            // (profiles/r05_convT_class_ab.txt; non-temporal output stores, measured beside it, lose: that launch +4 %)
             bx = (int)((((slot >> 1) * 8u + xcd) << 1) | (slot & 1u));
             if ((long)bx * sink.items >= (long)sink.tiles_j * sink.ncls) return;
         } else if (sink.xcd_map == 4) {
@@ -831,20 +753,10 @@ void igemm_kernel(P p, Q q, E e, int K, int klen, SplitSink sink) {
             const unsigned jl = slot / gridDim.y;
             by = (int)(slot - jl * gridDim.y); bx = (int)(jl * 8u + xcd);
             if ((long)bx * sink.items >= (long)sink.tiles_j * sink.ncls) return;
-        } else
-#if MVAE_XCD_ROWS
-        if (sink.xcd_map == 2) {
-            // row bands: XCD x owns rows [x * tiles_i / 8, (x + 1) * tiles_i / 8) x ALL column tiles -- the layer behind
-            // this one (same rows, same bands) then finds its whole input in the L2 that produced it
-            const unsigned sj = gridDim.x, si = gridDim.y >> 3;
+        } else {
+            const unsigned sj = gridDim.x >> 1, si = gridDim.y >> 2;
             const unsigned ti = slot / sj, tj = slot - ti * sj;
-            bx = (int)tj; by = (int)(xcd * si + ti);
-        } else
-#endif
-        {
-        const unsigned sj = gridDim.x >> 1, si = gridDim.y >> 2;
-        const unsigned ti = slot / sj, tj = slot - ti * sj;
-        bx = (int)((xcd & 1u) * sj + tj); by = (int)((xcd >> 1) * si + ti);
+            bx = (int)((xcd & 1u) * sj + tj); by = (int)((xcd >> 1) * si + ti);
         }
     }
     // Multi-item blocks (sink.items > 1, conv forms with short reductions): the block owns `n_items` consecutive
@@ -878,17 +790,6 @@ void igemm_kernel(P p, Q q, E e, int K, int klen, SplitSink sink) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
 
-#if MVAE_STAGGER
-    // experiment: de-phase the blocks that share a CU (block b lands in slot (b / 256) % 4 of its CU when the
-    // grid is dispatched in order), so that their non-MFMA phases do not coincide
-    {
-        const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-        const unsigned slot = (lin >> 8) & 3u;
-        if (slot == 1) __builtin_amdgcn_s_sleep(MVAE_STAGGER);
-        else if (slot == 2) __builtin_amdgcn_s_sleep(2 * MVAE_STAGGER);
-        else if (slot == 3) __builtin_amdgcn_s_sleep(3 * MVAE_STAGGER);
-    }
-#endif
     p.init(i0, t, cls);
     q.init(j0, t, cls);
     e.set_class(cls);
@@ -896,7 +797,7 @@ void igemm_kernel(P p, Q q, E e, int K, int klen, SplitSink sink) {
     // pre-activation, the dropout mask -- is fetched NOW and lands behind the whole reduction (EpRowMajor::fetch)
     // (up to four outputs per thread: the 256-thread variants would hold eight -- 24 registers, an occupancy step)
     constexpr bool COOP_PRE = KW > 1 && WGM * WGN < 4 && ep_prefetch<E>::value && (BM * BN) % NT == 0 &&
-                              (BM * BN) / NT <= (E::ROWRED ? 8 : 4) && MVAE_EPI_PREFETCH && (!E::ROWRED || MVAE_EPI_PREFETCH_ROWRED);
+                              (BM * BN) / NT <= (E::ROWRED ? 8 : 4);
     constexpr int CNE = COOP_PRE ? (BM * BN) / NT : 1;
     typename ep_pre<E>::type cpre[CNE];
     if constexpr (COOP_PRE) {
@@ -944,16 +845,10 @@ void igemm_kernel(P p, Q q, E e, int K, int klen, SplitSink sink) {
             if (Q::RMAJOR) qb[y] = Q::frag(Qs(buf), krow(0), (wj * WN + y) * 32 + lcol);
             else sb[y] = Qs(buf)[krow(0)][(wj * WN + y) * 32 + lcol];
         }
-#if MVAE_KO >= 4
-#pragma unroll
-        for (int x = 0; x < WM; ++x) { pa_n[x] = pa[x]; sa_n[x] = sa[x]; }
-#pragma unroll
-        for (int y = 0; y < WN; ++y) { qb_n[y] = qb[y]; sb_n[y] = sb[y]; }
-#endif
 #pragma unroll
         for (int st = 0; st < NS; ++st) {
             const int j = st & 3;
-            if (MVAE_KO < 4 && j == 0 && st + 4 < NS) { // row-major operands: the next chunk, a chunk ahead
+            if (j == 0 && st + 4 < NS) {              // row-major operands: the next chunk, a chunk ahead
 #pragma unroll
                 for (int x = 0; x < WM; ++x)
                     if (P::RMAJOR) pa_n[x] = P::frag(Ps(buf), krow(st + 4), (wi * WM + x) * 32 + lcol);
@@ -961,7 +856,7 @@ void igemm_kernel(P p, Q q, E e, int K, int klen, SplitSink sink) {
                 for (int y = 0; y < WN; ++y)
                     if (Q::RMAJOR) qb_n[y] = Q::frag(Qs(buf), krow(st + 4), (wj * WN + y) * 32 + lcol);
             }
-            if (MVAE_KO < 4 && st + 1 < NS) {           // k-major operands: the next step's values
+            if (st + 1 < NS) {                         // k-major operands: the next step's values
 #pragma unroll
                 for (int x = 0; x < WM; ++x)
                     if (!P::RMAJOR) sa_n[x] = Ps(buf)[krow(st + 1)][(wi * WM + x) * 32 + lcol];
@@ -970,9 +865,6 @@ void igemm_kernel(P p, Q q, E e, int K, int klen, SplitSink sink) {
                     if (!Q::RMAJOR) sb_n[y] = Qs(buf)[krow(st + 1)][(wj * WN + y) * 32 + lcol];
             }
             __builtin_amdgcn_sched_barrier(0);
-#if MVAE_SETPRIO
-            __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
             for (int x = 0; x < WM; ++x)
 #pragma unroll
@@ -981,9 +873,6 @@ void igemm_kernel(P p, Q q, E e, int K, int klen, SplitSink sink) {
                     const float bv = !Q::RMAJOR ? sb[y] : j == 0 ? qb[y].x : j == 1 ? qb[y].y : j == 2 ? qb[y].z : qb[y].w;
                     acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[x][y], 0, 0, 0);
                 }
-#if MVAE_SETPRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
             __builtin_amdgcn_sched_barrier(0);
             hook(st, NS);                               // a slice of the next tile's loads / stores, in this group's shadow
             __builtin_amdgcn_sched_barrier(0);
@@ -1011,7 +900,7 @@ void igemm_kernel(P p, Q q, E e, int K, int klen, SplitSink sink) {
     // wave's OWN matrix instructions.  With load(); compute(); store() as three phases a wave issues no MFMA
     // for a few hundred cycles per k-step and the pipe idles unless another block's wave happens to be in its
     // MFMA phase (tools/mfma_peak: the pipe itself sustains 154.6 TFLOP/s from one wave per SIMD).
-    constexpr bool CAN_IL = (NT == NTHREADS) && P::PARTS && Q::PARTS && MVAE_INTERLEAVE;
+    constexpr bool CAN_IL = (NT == NTHREADS) && P::PARTS && Q::PARTS;
     // block-uniform: the buffer path covers the block's k range (row loaders also take a partial last tile)
     const bool full = nsteps > 0 && ((kend - kbeg) % BKK == 0 || (P::TAIL && Q::TAIL)) && p.fast && q.fast;
     const bool il = CAN_IL && full;
@@ -1177,10 +1066,10 @@ void igemm_kernel(P p, Q q, E e, int K, int klen, SplitSink sink) {
                     const int kn = kof(g + 1), nb = (g + 1) & 1;
                     compute(g & 1, [&](int st, int ns) {
                         const int nl = (WM * WN >= 4) ? ns / 4 : ns / 8;
-                        if (MVAE_KO < 1 && st < nl) { p.load_part(kn, kend, t, pr0, st, nl); q.load_part(kn, kend, t, qr0, st, nl); }
-                        if (MVAE_KO < 2 && st >= ns - nl) { p.store_part(Ps(nb), t, pr0, st - (ns - nl), nl); q.store_part(Qs(nb), t, qr0, st - (ns - nl), nl); }
+                        if (st < nl) { p.load_part(kn, kend, t, pr0, st, nl); q.load_part(kn, kend, t, qr0, st, nl); }
+                        if (st >= ns - nl) { p.store_part(Ps(nb), t, pr0, st - (ns - nl), nl); q.store_part(Qs(nb), t, qr0, st - (ns - nl), nl); }
                     });
-                    if (MVAE_KO < 3) __syncthreads();
+                    __syncthreads();
                     if (last) finish_item(g / nsteps);
                 }
                 compute((G - 1) & 1, no_hook);
@@ -1200,10 +1089,10 @@ void igemm_kernel(P p, Q q, E e, int K, int klen, SplitSink sink) {
                 const int k2 = kof(g + 2);
                 compute(0, [&](int st, int ns) {
                     const int nl = ns / 2;
-                    if (st < nl) { if (MVAE_KO < 1) { p.load_part(k2, kend, t, pr0, st, nl); q.load_part(k2, kend, t, qr0, st, nl); } }
-                    else if (MVAE_KO < 2) { p.store_part(Ps(1), t, pr1, st - nl, ns - nl); q.store_part(Qs(1), t, qr1, st - nl, ns - nl); }
+                    if (st < nl) { p.load_part(k2, kend, t, pr0, st, nl); q.load_part(k2, kend, t, qr0, st, nl); }
+                    else { p.store_part(Ps(1), t, pr1, st - nl, ns - nl); q.store_part(Qs(1), t, qr1, st - nl, ns - nl); }
                 });
-                if (MVAE_KO < 3) __syncthreads();
+                __syncthreads();
                 if ((g + 1) % nsteps == 0) finish_item(g / nsteps);
                 // odd step g+1 on buffer 1: fetch tile g+3 into set 1 (the last tile again when there is none), stage
                 // tile g+2 (set 0) in buffer 0
@@ -1212,10 +1101,10 @@ void igemm_kernel(P p, Q q, E e, int K, int klen, SplitSink sink) {
                 const int k3 = kof(more3 ? g + 3 : g + 2);
                 compute(1, [&](int st, int ns) {
                     const int nl = ns / 2;
-                    if (st < nl) { if (MVAE_KO < 1) { p.load_part(k3, kend, t, pr1, st, nl); q.load_part(k3, kend, t, qr1, st, nl); } }
-                    else if (MVAE_KO < 2) { p.store_part(Ps(0), t, pr0, st - nl, ns - nl); q.store_part(Qs(0), t, qr0, st - nl, ns - nl); }
+                    if (st < nl) { p.load_part(k3, kend, t, pr1, st, nl); q.load_part(k3, kend, t, qr1, st, nl); }
+                    else { p.store_part(Ps(0), t, pr0, st - nl, ns - nl); q.store_part(Qs(0), t, qr0, st - nl, ns - nl); }
                 });
-                if (MVAE_KO < 3) __syncthreads();
+                __syncthreads();
                 if ((g + 2) % nsteps == 0) finish_item((g + 1) / nsteps);
             }
             // tail: tile g is staged in buffer 0; tile g+1 (if any) waits in register set 1
@@ -1242,16 +1131,10 @@ void igemm_kernel(P p, Q q, E e, int K, int klen, SplitSink sink) {
             const int kn = kbeg + (s + 1) * BKK, nb = (s + 1) & 1;
             compute(s & 1, [&](int st, int ns) {
                 const int nl = (WM * WN >= 4) ? ns / 4 : ns / 8;   // load slots at the head, store slots at the tail: >= 1500 MFMA cycles apart
-#if MVAE_KO < 1
                 if (st < nl) { p.load_part(kn, kend, t, pr0, st, nl); q.load_part(kn, kend, t, qr0, st, nl); }
-#endif
-#if MVAE_KO < 2
                 if (st >= ns - nl) { p.store_part(Ps(nb), t, pr0, st - (ns - nl), nl); q.store_part(Qs(nb), t, qr0, st - (ns - nl), nl); }
-#endif
             });
-#if MVAE_KO < 3
             __syncthreads();
-#endif
         }
         compute((nsteps - 1) & 1, no_hook);
         __syncthreads();
@@ -1267,16 +1150,16 @@ void igemm_kernel(P p, Q q, E e, int K, int klen, SplitSink sink) {
             const int k2 = kbeg + (s + 2) * BKK, k3 = kbeg + min(s + 3, nsteps - 1) * BKK;
             compute(0, [&](int st, int ns) {
                 const int nl = ns / 2;
-                if (st < nl) { if (MVAE_KO < 1) { p.load_part(k2, kend, t, pr0, st, nl); q.load_part(k2, kend, t, qr0, st, nl); } }
-                else if (MVAE_KO < 2) { p.store_part(Ps(1), t, pr1, st - nl, ns - nl); q.store_part(Qs(1), t, qr1, st - nl, ns - nl); }
+                if (st < nl) { p.load_part(k2, kend, t, pr0, st, nl); q.load_part(k2, kend, t, qr0, st, nl); }
+                else { p.store_part(Ps(1), t, pr1, st - nl, ns - nl); q.store_part(Qs(1), t, qr1, st - nl, ns - nl); }
             });
-            if (MVAE_KO < 3) __syncthreads();
+            __syncthreads();
             compute(1, [&](int st, int ns) {
                 const int nl = ns / 2;
-                if (st < nl) { if (MVAE_KO < 1) { p.load_part(k3, kend, t, pr1, st, nl); q.load_part(k3, kend, t, qr1, st, nl); } }
-                else if (MVAE_KO < 2) { p.store_part(Ps(0), t, pr0, st - nl, ns - nl); q.store_part(Qs(0), t, qr0, st - nl, ns - nl); }
+                if (st < nl) { p.load_part(k3, kend, t, pr1, st, nl); q.load_part(k3, kend, t, qr1, st, nl); }
+                else { p.store_part(Ps(0), t, pr0, st - nl, ns - nl); q.store_part(Qs(0), t, qr0, st - nl, ns - nl); }
             });
-            if (MVAE_KO < 3) __syncthreads();
+            __syncthreads();
         }
         // tail: tile s is staged in buffer 0; tile s+1 (if any) waits in register set 1
         if (s + 1 < nsteps) {
@@ -1315,19 +1198,20 @@ void igemm_kernel(P p, Q q, E e, int K, int klen, SplitSink sink) {
                 }
                 return;
             }
-            // PRELOAD (full k-tiles through the buffer path): EVERY wave issues the tile loads, unconditionally -- the
-            // MFMA-only waves with all offsets out of range, the last trips on the last tile again.  With
-            // `if (mover && s + 2 < nsteps) LOAD(...)` the waves that skip the loads reach the stores' wait with fewer
-            // operations outstanding, the compiler's wait counts are the minimum over both paths, and the movers wait
-            // for the loads they have only just issued: vmcnt(5) .. vmcnt(0) where 11 .. 6 would do -- ONE tile in flight
-            // instead of two, a full load latency per k-step (8 MFMAs per wave) in the 512-wide MLP layers.
-            constexpr bool PRELOAD = decltype(fullc)::value && ld_can_disable<P>::value && ld_can_disable<Q>::value &&
-                                     MVAE_PHASED_PRELOAD;
+            // PRELOAD (full k-tiles through the buffer path): the movers issue the tile loads unconditionally (the last trips
+            // on the last tile again) in a copy of the loop of their own.  With `if (mover && s + 2 < nsteps) LOAD(...)` the
+            // waves that skip the loads reach the stores' wait with fewer operations outstanding, the compiler's wait counts
+            // are the minimum over both paths, and the movers wait for the loads they have only just issued: ONE tile in
+            // flight instead of two, a full load latency per k-step (8 MFMAs per wave) in the 512-wide MLP layers.  x3
+            // interleaved (profiles/r05_mnist_switches_ab.txt): 0.2874 / 0.2897 / 0.2854 ms before, 0.2780 / 0.2837 / 0.2837
+            // with the two copies (every wave issuing loads, the MFMA-only ones out of range: 0.2918 / 0.2928 / 0.2896).
+            // Two register sets, not four: four make the launch faster and MNIST's step 9 % slower (171 registers).
+            constexpr bool PRELOAD = decltype(fullc)::value && ld_movers_loop<P>::value && ld_movers_loop<Q>::value;
             if constexpr (PRELOAD) {
                 if (nsteps <= 0) return;
                 auto tile_k = [&](int s2) { return kbeg + min(s2, nsteps - 1) * BKK; };
-                if (MVAE_PHASED_PRELOAD == 2 && !mover) {
-                    // variant 2: the MFMA-only waves run their own copy of the loop -- the same barriers, no loads --
+                if (!mover) {
+                    // the MFMA-only waves run their own copy of the loop -- the same barriers, no loads --
                     // so the movers' copy has no control-flow merge between its loads and its stores at all
                     __syncthreads();
                     int s = 0;
@@ -1343,71 +1227,19 @@ void igemm_kernel(P p, Q q, E e, int K, int klen, SplitSink sink) {
                     }
                     return;
                 }
-                if constexpr (MVAE_PHASED_PRELOAD == 2 && MVAE_PHASED_DEPTH == 4 && P::TAIL && Q::TAIL) {
-                    // FOUR tiles in flight in the movers' registers (only movers get here).  A k-step of these layouts is 8
-                    // MFMAs per wave -- 0.2 us -- against ~1 us for an L2 / fabric round trip: with two tiles ahead a step
-                    // still ends waiting for its successor's loads (MNIST's 1024 x 512 x 512 launches: 13.2 us for 3.4 us
-                    // of matrix time, profiles/r05_mnist_by_shape.txt).  A 512-thread block runs two waves per SIMD, so a
-                    // mover may hold 256 registers: four (P, Q) register sets.  Tiles beyond the reduction are requested
-                    // at their own k: the row loaders' TAIL rule turns every such load into an out-of-range one -- no
-                    // traffic, zeros nobody stages.  Same barriers as the load-free copy above: 1 + nsteps.
-                    typename P::Regs pr2, pr3;
-                    typename Q::Regs qr2, qr3;
-                    auto tk = [&](int s2) { return kbeg + s2 * BKK; };
-                    LOAD(fullc, tk(0), pr0, qr0); LOAD(fullc, tk(1), pr1, qr1);
-                    LOAD(fullc, tk(2), pr2, qr2); LOAD(fullc, tk(3), pr3, qr3);
-                    STORE(fullc, 0, pr0, qr0);
-                    __syncthreads();
-                    int s = 0;
-                    for (; s + 3 < nsteps; s += 4) {
-                        LOAD(fullc, tk(s + 4), pr0, qr0);
-                        compute(0, no_hook);
-                        STORE(fullc, 1, pr1, qr1);
-                        __syncthreads();
-                        LOAD(fullc, tk(s + 5), pr1, qr1);
-                        compute(1, no_hook);
-                        STORE(fullc, 0, pr2, qr2);
-                        __syncthreads();
-                        LOAD(fullc, tk(s + 6), pr2, qr2);
-                        compute(0, no_hook);
-                        STORE(fullc, 1, pr3, qr3);
-                        __syncthreads();
-                        LOAD(fullc, tk(s + 7), pr3, qr3);
-                        compute(1, no_hook);
-                        if (s + 4 < nsteps) STORE(fullc, 0, pr0, qr0);
-                        __syncthreads();
-                    }
-                    const int left = nsteps - s;        // 0 .. 3 steps: tile s sits in buffer 0, s + 1 / s + 2 in sets 1 / 2
-                    if (left >= 1) {
-                        compute(0, no_hook);
-                        if (left >= 2) STORE(fullc, 1, pr1, qr1);
-                        __syncthreads();
-                    }
-                    if (left >= 2) {
-                        compute(1, no_hook);
-                        if (left >= 3) STORE(fullc, 0, pr2, qr2);
-                        __syncthreads();
-                    }
-                    if (left >= 3) {
-                        compute(0, no_hook);
-                        __syncthreads();
-                    }
-                    return;
-                }
-                if (!mover) { loader_disable<PRELOAD>(p); loader_disable<PRELOAD>(q); }     // variant 1
                 LOAD(fullc, tile_k(0), pr0, qr0);
                 LOAD(fullc, tile_k(1), pr1, qr1);
-                if (mover) STORE(fullc, 0, pr0, qr0);
+                STORE(fullc, 0, pr0, qr0);
                 __syncthreads();
                 int s = 0;
                 for (; s + 1 < nsteps; s += 2) {
                     LOAD(fullc, tile_k(s + 2), pr0, qr0);
                     compute(0, no_hook);
-                    if (mover) STORE(fullc, 1, pr1, qr1);
+                    STORE(fullc, 1, pr1, qr1);
                     __syncthreads();
                     LOAD(fullc, tile_k(s + 3), pr1, qr1);
                     compute(1, no_hook);
-                    if (mover && s + 2 < nsteps) STORE(fullc, 0, pr0, qr0);
+                    if (s + 2 < nsteps) STORE(fullc, 0, pr0, qr0);
                     __syncthreads();
                 }
                 if (s < nsteps) {   // odd number of k-steps: the last tile sits in buffer 0
@@ -1442,7 +1274,7 @@ void igemm_kernel(P p, Q q, E e, int K, int klen, SplitSink sink) {
                 __syncthreads();
             }
         };
-        constexpr bool CAN_FULL = P::PARTS && Q::PARTS && MVAE_INTERLEAVE;
+        constexpr bool CAN_FULL = P::PARTS && Q::PARTS;
         if (CAN_FULL && full) {
             if constexpr (CAN_FULL) phased(std::true_type{});
         } else {
@@ -1596,21 +1428,8 @@ void igemm_kernel(P p, Q q, E e, int K, int klen, SplitSink sink) {
 #pragma unroll
         for (int x = 0; x < WM; ++x) {
             const int ib = i0 + (wi * WM + x) * 32 + 4 * lrow;
-            if constexpr (ep_prefetch<E>::value && MVAE_EPI_BATCH) {
-                // operands of eight outputs at a time, all fetched before the first is used (see EpRowMajor::fetch: left
-                // inside put(), every output waits out its own memory latency behind a block-uniform branch)
-                if (!partial) {
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        typename ep_pre<E>::type pr[8];
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) pr[r] = e.fetch(ib + (r & 3) + 8 * ((8 * h + r) >> 2), j);
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) e.put_pre(ib + (r & 3) + 8 * ((8 * h + r) >> 2), j, acc[x][y][8 * h + r], pr[r]);
-                    }
-                    continue;
-                }
-            }
+            // (the operands of eight outputs fetched together, as in EpRowMajor::fetch, gain nothing here: with 3-5 blocks per CU the
+            //  other blocks' matrix work already covers a block's epilogue -- CelebA +0.6 %, FashionMNIST +0.1 %, profiles/r04_epilogue_ab.txt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int i = ib + (r & 3) + 8 * (r >> 2);
@@ -1699,32 +1518,18 @@ __global__ __launch_bounds__(256) void finish_few_vec_kernel(SplitSink sink, int
     }
     const int i = (int)(idx / jq), j = (int)(idx - (size_t)i * jq) * 4;
     const float *src = sink.ws + (size_t)i * sink.J + j;
-    // MVAE_FINISH_PREFETCH (off): the four outputs' bias / pre-activation / mask requested before the partial sums instead
-    // of one by one inside put() (this kernel is 2 % of the FashionMNIST and CelebA steps).  Parity green, one
-    // step pair 2.3041 -> 2.3018 ms on FashionMNIST: nothing measurable (profiles/r04_epilogue_ab.txt).
-    constexpr bool PRE = ep_prefetch<E>::value && !E::ROWRED && MVAE_FINISH_PREFETCH;
-    typename ep_pre<E>::type pre[4];
-    if constexpr (PRE) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) pre[c] = e.fetch(i, j + c);
-    }
+    // (requesting the four outputs' bias / pre-activation / mask before the partial sums instead of inside put() measured
+    //  nothing: one step pair 2.3041 -> 2.3018 ms on FashionMNIST, profiles/r04_epilogue_ab.txt)
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll 4
     for (int z = 0; z < splits; ++z) {       // four loads in flight, added in split order
         const float4 v = *reinterpret_cast<const float4 *>(src + (size_t)z * sink.stride);
         s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
     }
-    if constexpr (PRE) {
-        if (e.col(j)) e.put_pre(i, j, s.x, pre[0]);
-        if (e.col(j + 1)) e.put_pre(i, j + 1, s.y, pre[1]);
-        if (e.col(j + 2)) e.put_pre(i, j + 2, s.z, pre[2]);
-        if (e.col(j + 3)) e.put_pre(i, j + 3, s.w, pre[3]);
-    } else {
-        if (e.col(j)) e.put(i, j, s.x);
-        if (e.col(j + 1)) e.put(i, j + 1, s.y);
-        if (e.col(j + 2)) e.put(i, j + 2, s.z);
-        if (e.col(j + 3)) e.put(i, j + 3, s.w);
-    }
+    if (e.col(j)) e.put(i, j, s.x);
+    if (e.col(j + 1)) e.put(i, j + 1, s.y);
+    if (e.col(j + 2)) e.put(i, j + 2, s.z);
+    if (e.col(j + 3)) e.put(i, j + 3, s.w);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1864,7 +1669,6 @@ int launch_igemm_impl(Plan pl, PF make_p, QF make_q, E e, int I, int J, int K, S
         dim3 grid(((J + TN - 1) / TN) * sink.ncls, (I + TM - 1) / TM, pl.splits);                \
         sink.tiles_j = (J + TN - 1) / TN;                                                        \
         sink.xcd_map = (pl.xcd == 1 && sink.ncls == 1 && pl.splits == 1 && grid.x % 2 == 0 && grid.y % 4 == 0) ? 1 : 0; \
-        if (MVAE_XCD_ROWS && pl.xcd == 1 && sink.ncls == 1 && pl.splits == 1 && grid.y % 8 == 0) sink.xcd_map = 2; \
         if (pl.xcd == 4 && pl.splits >= 8) { sink.xcd_map = 4; grid.z = (grid.z + 7) / 8 * 8; } /* k ranges XCD-local */ \
         sink.items = 1;                                                                          \
         if (pl.items > 1 && E::MULTI && KW == 1 && !ROWSUM && pl.splits == 1 && NT == NTHREADS && K % PLD<TM>::BKV == 0 && \
@@ -1877,7 +1681,7 @@ int launch_igemm_impl(Plan pl, PF make_p, QF make_q, E e, int I, int J, int K, S
         if (pl.xcd == 3 && pl.splits == 1 && grid.y > 1 && grid.x >= 64) {                      \
             sink.xcd_map = 3; grid.x = (grid.x + 7) / 8 * 8;    /* (class, j tile) items XCD-local */ \
         }                                                                                        \
-        if (MVAE_PAIR_NEIGH && E::PAIR && WM * WN == 1 && sink.items > 1 && sink.ncls == 4 && sink.cls_minor && grid.y == 1 && \
+        if (E::PAIR && WM * WN == 1 && sink.items > 1 && sink.ncls == 4 && sink.cls_minor && grid.y == 1 && \
             pl.splits == 1 && sink.xcd_map == 0) {                                                \
             sink.items = 2; sink.xcd_map = 5;                                                    \
             grid.x = ((unsigned)sink.tiles_j * 2u + 15u) / 16u * 16u;                            \

@@ -4,9 +4,6 @@
 #include "gemm2.h"
 #include "linear_direct.h"
 
-#ifndef MVAE_XCD_MAP
-#define MVAE_XCD_MAP 1          // Linear launches: XCD-local output sub-grids (gemm_core.h, igemm_kernel)
-#endif
 
 
 // ==========================================================================================
@@ -51,7 +48,7 @@ static int linear_fwd_impl(const float *x, int ldx, const float *w, const float 
     // gr: a = x stride, b = w stride, c = bias stride, d = pre/act stride
     const bool vec = aligned16(x) && aligned16(w) && ldx % 4 == 0 && K % 4 == 0 && gr.a % 4 == 0 && gr.b % 4 == 0;
     Plan pl = make_plan(M, N, K, ws != nullptr, PLAN_FWD, gr.G, vec);
-    pl.xcd = MVAE_XCD_MAP;
+    pl.xcd = 1;                    // XCD-local output sub-grids (gemm_core.h, igemm_kernel)
     SplitSink sink = make_sink(ws, M, N, false);
     sink.ncls = gr.G; sink.cls_region = (size_t)pl.splits * sink.stride;
     if (pl.splits > 1 && ws_bytes < gr.G * sink.cls_region * sizeof(float)) return MVAE_ERR_WS;
@@ -81,7 +78,7 @@ static int linear_loss_impl(const float *x, int ldx, const float *w, E e, int M,
     const bool vec = aligned16(x) && aligned16(w) && ldx % 4 == 0 && K % 4 == 0;
     Plan pl = make_plan(M, N, K, false, PLAN_FWD, 1, vec);
     if (pl.splits != 1) return MVAE_ERR_ARG;
-    pl.xcd = MVAE_XCD_MAP;
+    pl.xcd = 1;
     SplitSink sink = make_sink(nullptr, M, N, false);
     sink.ncls = 1; sink.cls_region = 0;
     auto mp = [&](auto &p) { p.src = x; p.ld = ldx; p.R = M; p.Klen = K; p.cls_stride = 0; };
@@ -139,7 +136,7 @@ static int linear_dgrad_impl(const float *dy, int lddy, const float *w, float *d
     const bool vec = aligned16(dy) && aligned16(w) && lddy % 4 == 0 && N % 4 == 0 && K % 4 == 0 && gr.a % 4 == 0 &&
                      gr.b % 4 == 0;
     Plan pl = make_plan(M, K, N, ws != nullptr, PLAN_FWD, gr.G, vec);
-    pl.xcd = MVAE_XCD_MAP;
+    pl.xcd = 1;
     SplitSink sink = make_sink(ws, M, K, false);
     sink.ncls = gr.G; sink.cls_region = (size_t)pl.splits * sink.stride;
     if (pl.splits > 1 && ws_bytes < gr.G * sink.cls_region * sizeof(float)) return MVAE_ERR_WS;
@@ -174,7 +171,7 @@ static int linear_wgrad_impl(const float *dy, int lddy, const float *x, int ldx,
     const bool vec = aligned16(dy) && aligned16(x) && lddy % 4 == 0 && ldx % 4 == 0 && N % 4 == 0 && K % 4 == 0 &&
                      gr.a % 4 == 0 && gr.b % 4 == 0;
     Plan pl = make_plan(N, K, M, ws != nullptr, PLAN_LIN_WGRAD, gr.G, vec);
-    pl.xcd = MVAE_XCD_MAP;
+    pl.xcd = 1;
     SplitSink sink = make_sink(ws, N, K, db != nullptr);
     sink.ncls = gr.G; sink.cls_region = (size_t)pl.splits * sink.stride;
     if (pl.splits > 1 && ws_bytes < gr.G * sink.cls_region * sizeof(float)) return MVAE_ERR_WS;

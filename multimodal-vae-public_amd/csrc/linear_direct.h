@@ -265,30 +265,15 @@ template <int KW, bool ADAM> __device__ __forceinline__ void wgrad_batched_body(
 //     an XCD's resident blocks share one or two row bands of dy and sweep x together;
 //   * fewer, larger blocks (<= 2 per CU through the LDS footprint of the final reduction) leave wave slots, registers
 //     and LDS on every CU for a chain kernel that arrives while the batch is running.
-#ifndef MVAE_WGRAD2
-#define MVAE_WGRAD2 1            // 0: the round-4 batch kernel (wgrad_batched_kernel) for every launch
-#endif
-#ifndef MVAE_WB2_KO
-#define MVAE_WB2_KO 0
-#endif
-#ifndef MVAE_WB2_KW
-#define MVAE_WB2_KW 0            // A/B builds: force the waves per tile (2 .. 16)
-#endif
 #ifndef MVAE_WB2_PD22
 #define MVAE_WB2_PD22 1          // chunks of 8 rows per register set of the 64 x 64 wave tile.  2: ~150 registers; 1: 121 -- a chain kernel's
 #endif                           // 512-thread block (116-122 registers) then FITS BESIDE a batch block on a CU.  The launch alone is
                                  // the same (24.5 vs 24.8 us), the MNIST step 2 % faster (0.2789-0.2802 vs 0.2844-0.2860 ms, x4
                                  // interleaved, profiles/r05_wgrad_ab.txt): sharing a CU is what the step's two streams need,
-                                 // the same effect that makes four k-tiles in flight lose (gemm_core.h MVAE_PHASED_DEPTH)
+                                 // the same effect that makes four k-tiles in flight lose (gemm_core.h, the phased loop)
 #ifndef MVAE_WB2_PD11
 #define MVAE_WB2_PD11 2          // chunks per register set of the 32 x 32 wave tile: 2 (48-63 registers) instead of 4 (82-98): the launch
                                  // alone 19.8 -> 18.9 us (label decoder), 12.9 -> 11.8 us (image encoder); the step unchanged (x4)
-#endif
-#ifndef MVAE_WB2_PRIO
-#define MVAE_WB2_PRIO 0          // A/B builds: wave priority of the batch kernel (the batches sit on the side stream's chain)
-#endif
-#ifndef MVAE_WGRAD2_SHAPE
-#define MVAE_WGRAD2_SHAPE 0      // 0: by tile count; 22 / 21 / 11: force the 64 x 64 / 64 x 32 / 32 x 32 wave tile (A/B builds)
 #endif
 
 constexpr int WB2_SEGS = 8;
@@ -355,18 +340,10 @@ __device__ __forceinline__ void wgrad_tile2(const WgradBatchItem &w, int tile_i,
             const i32x4_t ra = wb2_rsrc(ba, c * 8u * ulda, ext_a), rb = wb2_rsrc(bb, c * 8u * uldb, ext_b);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-#if MVAE_WB2_KO == 2        /* knock-out (results wrong): no loads -- the MFMA stream alone */
-                (void)ra; (void)rb;
-#pragma unroll
-                for (int f = 0; f < FM; ++f) asm volatile("" : "=v"(as[p][f][q]));
-#pragma unroll
-                for (int f = 0; f < FN; ++f) asm volatile("" : "=v"(bs[p][f][q]));
-#else
 #pragma unroll
                 for (int f = 0; f < FM; ++f) as[p][f][q] = buf_load1(ra, va[q] + 128 * f);
 #pragma unroll
                 for (int f = 0; f < FN; ++f) bs[p][f][q] = buf_load1(rb, vb[q] + 128 * f);
-#endif
             }
         }
     };
@@ -378,13 +355,8 @@ __device__ __forceinline__ void wgrad_tile2(const WgradBatchItem &w, int tile_i,
 #pragma unroll
                 for (int f = 0; f < FM; ++f)
 #pragma unroll
-                    for (int g = 0; g < FN; ++g) {
-#if MVAE_WB2_KO == 1        /* knock-out (results wrong): no MFMAs -- the load stream alone (the values are 'used') */
-                        asm volatile("" :: "v"(as[p][f][q]), "v"(bs[p][g][q]));
-#else
+                    for (int g = 0; g < FN; ++g)
                         acc[f][g] = __builtin_amdgcn_mfma_f32_32x32x2f32(as[p][f][q], bs[p][g][q], acc[f][g], 0, 0, 0);
-#endif
-                    }
             if constexpr (decltype(with_rs)::value) {
 #pragma unroll
                 for (int f = 0; f < FM; ++f) rs[f] += (as[p][f][0] + as[p][f][1]) + (as[p][f][2] + as[p][f][3]);
@@ -476,7 +448,6 @@ __global__ __launch_bounds__(64 * KW) void wgrad_batched2_kernel(WgradBatch2Args
     const int xcd = blockIdx.x & (WB2_SEGS - 1), slot = blockIdx.x >> 3;
     const int tile = a.seg[xcd] + slot;
     if (tile >= a.seg[xcd + 1]) return;
-    if (MVAE_WB2_PRIO) __builtin_amdgcn_s_setprio(MVAE_WB2_PRIO);
     int p = 0, first = 0;
 #pragma unroll 1
     for (int q = 0; q < a.n - 1; ++q) {
@@ -491,7 +462,6 @@ __global__ __launch_bounds__(64 * KW) void wgrad_batched2_kernel(WgradBatch2Args
 // Re-tile the table for FM x FN wave tiles, cut it into XCD segments, launch.  Returns false when the batch has an
 // item the v2 tile code does not take (none today: kept for the Adam-fused form, which stays on the old kernel).
 inline bool wgrad_batched2_launch(const WgradBatchArgs &a, hipStream_t st, int *status) {
-    if (!MVAE_WGRAD2) return false;
     long t22 = 0, t21 = 0, t11 = 0;
     int max_m = 0;
     for (int q = 0; q < a.n; ++q) {
@@ -514,7 +484,6 @@ inline bool wgrad_batched2_launch(const WgradBatchArgs &a, hipStream_t st, int *
     long busy = busy22;
     if (busy21 < busy) { shape = 21; busy = busy21; }
     if (busy11 < busy) { shape = 11; busy = busy11; }
-    if (MVAE_WGRAD2_SHAPE) shape = MVAE_WGRAD2_SHAPE;
     const long tiles = shape == 22 ? t22 : (shape == 21 ? t21 : t11);
     const int fm = shape == 11 ? 1 : 2, fn = shape == 22 ? 2 : 1;
     // waves per tile (they split the batch rows): ~2 per SIMD over the launch, at least 4 chunks of 8 rows each
@@ -522,7 +491,6 @@ inline bool wgrad_batched2_launch(const WgradBatchArgs &a, hipStream_t st, int *
     if (shape == 22 && kw < 4) kw = 4;
     while (kw > 2 && max_m < 8 * 4 * kw) kw >>= 1;
     if (shape == 11 && kw < 4) kw = 4;
-    if (MVAE_WB2_KW) kw = MVAE_WB2_KW;
     WgradBatch2Args b;
     b.n = a.n;
     int total = 0;

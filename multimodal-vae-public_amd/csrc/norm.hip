@@ -772,17 +772,11 @@ __global__ __launch_bounds__(BNF_THREADS) void bn_stats_merge_kernel(const float
     if (running_mean) { running_mean[c] = rm; running_var[c] = rv; }
 }
 
-#ifndef MVAE_BN_FUSED
-#define MVAE_BN_FUSED 1         // 0: every layer on the two-launch path (A/B builds)
-#endif
-#ifndef MVAE_BN_SLICE
-#define MVAE_BN_SLICE 1         // 0: slices of 16 K .. 64 K elements / many groups stay on the two-launch path (A/B builds)
-#endif
 constexpr int BNF_GMAX_FWD = 3, BNF_GMAX_BWD = 2, BN1_GMAX = 3;
 
 // which single-launch form takes the shape: 0 none, 1 spatial, 2 BatchNorm1d
 inline int bn_fused_kind(const BnShape &sh, bool bwd) {
-    if (!MVAE_BN_FUSED || (long)sh.B * sh.C * sh.HW >= (1L << 30)) return 0;
+    if ((long)sh.B * sh.C * sh.HW >= (1L << 30)) return 0;
     if (sh.HW == 1) return (sh.G <= BN1_GMAX && sh.B <= BN1_TY * BN1_MAX_ROWS) ? 2 : 0;
     // (unaligned / odd-width maps keep one element per register: half the slice when several groups share the block)
     const int max_n = (!sh.vec && sh.G > 1) ? BNF_MAX_N / 2 : BNF_MAX_N;
@@ -793,7 +787,7 @@ inline int bn_fused_kind(const BnShape &sh, bool bwd) {
     // 64 .. 128 slices (CelebA's own 16x16 layers) the 1024-thread blocks leave most CUs idle (13.8 -> 19.4 us), at
     // 16 K elements the two-launch path is already at 6 TB/s (75 -> 86 us), and the backward form (dh kept, x re-read)
     // lost everywhere it was tried (18.4 -> 34.4 us at 64 slices) and was removed.
-    return (!bwd && MVAE_BN_SLICE && sh.vec && sh.n > BNF_MAX_N && sh.n <= BNS_MAX_N && (long)sh.C * sh.G >= 512 &&
+    return (!bwd && sh.vec && sh.n > BNF_MAX_N && sh.n <= BNS_MAX_N && (long)sh.C * sh.G >= 512 &&
             sh.G <= 65535 && (sh.HW >> 2) <= BNF_THREADS && BNF_THREADS % (sh.HW >> 2) == 0) ? 3 : 0;
 }
 

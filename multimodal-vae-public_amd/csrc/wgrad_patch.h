@@ -24,9 +24,6 @@
 
 namespace {
 
-#ifndef MVAE_WGRAD_PATCH
-#define MVAE_WGRAD_PATCH 1          // 0: these layers stay on igemm_kernel<LdWgradDy, LdWgradX> (A/B builds)
-#endif
 #ifndef MVAE_WGRAD_PATCH_BLOCKS
 #define MVAE_WGRAD_PATCH_BLOCKS 512 // blocks a launch aims at (tiles x splits)
 #endif
@@ -160,7 +157,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_patch_kernel(const float *__rest
 // the launch for a layer, or false (the caller keeps the implicit-GEMM launch)
 inline bool wgrad_patch_plan(int B, int SC, int BC, int OH, int OW, const void *S, const void *L, void *ws, size_t ws_bytes,
                              WgradPatchGeo *g) {
-    if (!MVAE_WGRAD_PATCH) return false;
 #ifdef MVAE_TUNING
     if (getenv("MVAE_WGRAD_PATCH_OFF")) return false;
 #endif

@@ -65,7 +65,7 @@ def test_small_layout_epilogue_loads_only_the_accumulate_operand(linear_kernels,
     # one optional load per output is left behind the reduction: `if (accumulate) v += out[idx]`
     assert _loads_behind_last_mfma(lines) <= outputs, kernel
     # ... and the pre-activation / mask (and bias) of every output were requested before the first matrix instruction.
-    # (Since MVAE_PHASED_PRELOAD=2 the MFMA-only waves' load-free copy of the loop comes first in the text, so the movers'
+    # (The MFMA-only waves of a k-grouped block run a load-free copy of the loop, which comes first in the text, so the movers'
     # first tile loads are no longer textually ahead of the first v_mfma: what IS ahead of it is exactly the epilogue's
     # operand prefetch, issued before the waves part ways; the tile loads are counted over the whole kernel.)
     assert _loads_ahead_of_first_mfma(lines) >= 2 * outputs, kernel

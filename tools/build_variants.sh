@@ -22,6 +22,6 @@ while [ $# -ge 2 ]; do
     done
     wait
     $HIPCC --offload-arch=gfx950 -shared -fPIC -o ../libmvae_hip_tuning_$name.so $objs \
-        loss.o misc.o reparam.o gather.o preprocess.o comm.o gru.o -ldl
+        loss.o misc.o reparam.o gather.o preprocess.o comm.o gru.o conv_gen.o -ldl
     echo built libmvae_hip_tuning_$name.so
 done
