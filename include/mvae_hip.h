@@ -253,6 +253,86 @@ int mvae_convT2d_k4_fwd_stats(const float *x, const float *w, float *part, size_
 int mvae_conv_k4_route(int op, int B, int Cin, int H, int W, int Cout, int stride, int pad,
                        size_t ws_bytes, int *splits /* may be NULL */);
 
+/* Which kernel a Linear launch takes.  mvae_linear_fwd / _bce_fwd / _ce_fwd / _dgrad / _wgrad and their grouped forms pick
+ * one of the kernel instantiations below by tile counts, reduction length, operand alignment, output form and scratch
+ * size; this query runs the SAME route function the launch switches on, launches nothing, allocates nothing and touches
+ * no device.
+ *   op         the launch (MVAE_LOP_*); G = 1 for the single entry points (the fused losses have no grouped form)
+ *   M, N, K    as that launch's own arguments (rows, output features, input features)
+ *   ld_a, ld_b its two leading dimensions in the order of its argument list: (ldx, ldy) for the forwards, (lddy, lddx) for
+ *              the data gradient, (lddy, ldx) for the weight gradient
+ *   gs_a, gs_b the group strides of its two INPUT operands: (x, w), (dy, w), (dy, x); ignored for G = 1
+ *   aligned    non-zero: both input operands are 16-byte aligned (the scratch is taken to be: allocators align it)
+ *   fwd_form   MVAE_LOP_FWD only (MVAE_LFORM_*): which outputs the call stores
+ *   want_db    MVAE_LOP_WGRAD only: a bias gradient is asked for
+ *   ws_bytes   the scratch the launch would be given; 0 = none, i.e. ws = NULL: no split reduction
+ *   splits     (may be NULL) the number of reduction partials a finish launch sums, 1 where there is none
+ *   finish     (may be NULL) the launch that sums them (MVAE_LFINISH_*)
+ *   returns    a MVAE_LROUTE_* code, or what the launch itself would return for these arguments without launching:
+ *              MVAE_ERR_ARG (bad op / shape / leading dimension), MVAE_ERR_WS (scratch too small for the split plan).
+ * Forward and data gradient share the gemm2s ids (the kernel's Q_RK parameter follows the op), the fused losses and the
+ * weight gradient share the small igemm ids (the epilogue follows the op). */
+#define MVAE_LOP_FWD      0   /* mvae_linear_fwd, mvae_linear_fwd_grouped */
+#define MVAE_LOP_BCE_FWD  1   /* mvae_linear_bce_fwd */
+#define MVAE_LOP_CE_FWD   2   /* mvae_linear_ce_fwd */
+#define MVAE_LOP_DGRAD    3   /* mvae_linear_dgrad, mvae_linear_dgrad_grouped */
+#define MVAE_LOP_WGRAD    4   /* mvae_linear_wgrad, mvae_linear_wgrad_grouped */
+
+#define MVAE_LFORM_OTHER    0   /* pre alone, or act alone with a dropout mask */
+#define MVAE_LFORM_PRE_ACT  1   /* pre and act */
+#define MVAE_LFORM_ACT_ONLY 2   /* act alone, no mask */
+
+#define MVAE_LFINISH_NONE     0
+#define MVAE_LFINISH_FINISH   1   /* finish_kernel: more than 16 partials */
+#define MVAE_LFINISH_FEW      2   /* finish_few_kernel */
+#define MVAE_LFINISH_FEW_VEC  3   /* finish_few_vec_kernel: float4 partial loads */
+#define MVAE_LFINISH_G2       4   /* g2_finish_kernel (the persistent gemm2 modes: tuning builds only) */
+
+#define MVAE_LROUTE_GEMM2            1   /* gemm2_kernel, one 64 x 64 tile per block */
+#define MVAE_LROUTE_G2S_32x64_K4     2   /* gemm2s_kernel: tile 32 x 64, 4 k-groups of waves */
+#define MVAE_LROUTE_G2S_64x32_K4     3
+#define MVAE_LROUTE_G2S_32x64_K2     4
+#define MVAE_LROUTE_G2S_64x32_K2     5
+#define MVAE_LROUTE_G2S_32x32_K8     6
+#define MVAE_LROUTE_G2S_32x32_K4     7
+#define MVAE_LROUTE_IGS_64x32_K4     8   /* igemm_kernel, small layouts (BK = 64, float4 loaders) */
+#define MVAE_LROUTE_IGS_64x32_K2     9
+#define MVAE_LROUTE_IGS_32x64_K4    10
+#define MVAE_LROUTE_IGS_32x64_K2    11
+#define MVAE_LROUTE_IGS_32x32_K8    12
+#define MVAE_LROUTE_IGS_32x32_K4    13
+#define MVAE_LROUTE_IG_32x128       14   /* igemm_kernel, large layouts (BK = 32), float4 loaders: the narrow plan */
+#define MVAE_LROUTE_IG_128x128      15   /* the 128-row tiles: conv plans; a Linear launch takes them only when a tuning build forces the tile */
+#define MVAE_LROUTE_IG_128x64       16
+#define MVAE_LROUTE_IG_64x128       17
+#define MVAE_LROUTE_IG_64x64_K4     18
+#define MVAE_LROUTE_IG_64x64_K2     19
+#define MVAE_LROUTE_IG_64x64        20
+#define MVAE_LROUTE_IG_32x128_S     30   /* ... scalar loaders (an operand that float4 loads cannot take) */
+#define MVAE_LROUTE_IG_128x128_S    31
+#define MVAE_LROUTE_IG_128x64_S     32
+#define MVAE_LROUTE_IG_64x128_S     33
+#define MVAE_LROUTE_IG_64x64_K4_S   34
+#define MVAE_LROUTE_IG_64x64_K2_S   35
+#define MVAE_LROUTE_IG_64x64_S      36
+#define MVAE_LROUTE_DGRAD_SMALLN    40   /* dgrad_smalln_kernel: N <= 16 */
+#define MVAE_LROUTE_WGRAD_DIRECT_4  41   /* wgrad_direct_kernel, 4 waves per 32 x 32 tile */
+#define MVAE_LROUTE_WGRAD_DIRECT_8  42
+#define MVAE_LROUTE_WGRAD_DIRECT_16 43
+#define MVAE_LROUTE_WGRAD_BATCHED2      50   /* wgrad_batched2_kernel */
+#define MVAE_LROUTE_WGRAD_BATCHED       51   /* wgrad_batched_kernel */
+#define MVAE_LROUTE_WGRAD_BATCHED_ADAM  52   /* wgrad_batched_adam_kernel */
+int mvae_linear_route(int op, int G, int M, int N, int K, int ld_a, int ld_b, size_t gs_a, size_t gs_b, int aligned,
+                      int fwd_form, int want_db, size_t ws_bytes, int *splits /* may be NULL */,
+                      int *finish /* may be NULL */);
+/* The same for mvae_linear_wgrad_batched (adam = 0) / mvae_linear_wgrad_batched_adam (adam != 0) on an item table: the
+ * items' pointers are only compared with NULL and with one another, never dereferenced.
+ *   tile_rows, tile_cols, waves  (each may be NULL) the output tile a block computes and the waves that share it
+ *   returns    MVAE_LROUTE_WGRAD_BATCHED2 / _BATCHED / _BATCHED_ADAM, or MVAE_ERR_ARG where the launch refuses the table
+ *              (the Adam form's checks of its mvae_adam_fuse argument are not part of the table and not repeated here). */
+int mvae_linear_wgrad_batched_route(const mvae_wgrad_item *items, int n_items, int adam, int *tile_rows /* may be NULL */,
+                                    int *tile_cols /* may be NULL */, int *waves /* may be NULL */);
+
 /* ------------------------------------------------------------------------------------
  * K17 General stride-2 conv family (csrc/conv_gen.hip): Conv2d / ConvTranspose2d with a square kernel
  *     ks in {4, 5}, stride 2, pad in {0, 1}, bias=False, ANY map size (odd, non-square) with

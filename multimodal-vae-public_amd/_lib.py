@@ -33,6 +33,21 @@ CONV_ROUTES = {1: 'igemm', 2: 'igemm_pair', 3: 'gemm2', 4: 'conv_patch', 5: 'sma
                13: 'patch8', 14: 'patch7', 15: 'patch16', 16: 'patch_stats', 17: 'wgrad_smallcin',
                18: 'wgrad_smallcin2', 19: 'wgrad_patch'}
 
+# mvae_linear_route / mvae_linear_wgrad_batched_route: the launches (MVAE_LOP_*), the forward's output forms
+# (MVAE_LFORM_*), the kernels (MVAE_LROUTE_*) and the launches that sum split partials (MVAE_LFINISH_*)
+LINEAR_OPS = {'fwd': 0, 'bce_fwd': 1, 'ce_fwd': 2, 'dgrad': 3, 'wgrad': 4}
+LINEAR_FORMS = {'other': 0, 'pre+act': 1, 'act': 2}
+LINEAR_FINISH = {0: None, 1: 'finish', 2: 'finish_few', 3: 'finish_few_vec', 4: 'g2_finish'}
+LINEAR_ROUTES = {1: 'gemm2', 2: 'g2s_32x64_k4', 3: 'g2s_64x32_k4', 4: 'g2s_32x64_k2', 5: 'g2s_64x32_k2',
+                 6: 'g2s_32x32_k8', 7: 'g2s_32x32_k4', 8: 'igs_64x32_k4', 9: 'igs_64x32_k2', 10: 'igs_32x64_k4',
+                 11: 'igs_32x64_k2', 12: 'igs_32x32_k8', 13: 'igs_32x32_k4', 14: 'ig_32x128', 15: 'ig_128x128',
+                 16: 'ig_128x64', 17: 'ig_64x128',
+                 18: 'ig_64x64_k4', 19: 'ig_64x64_k2', 20: 'ig_64x64', 30: 'ig_32x128_s', 31: 'ig_128x128_s',
+                 32: 'ig_128x64_s', 33: 'ig_64x128_s',
+                 34: 'ig_64x64_k4_s', 35: 'ig_64x64_k2_s', 36: 'ig_64x64_s', 40: 'dgrad_smalln', 41: 'wgrad_direct_4',
+                 42: 'wgrad_direct_8', 43: 'wgrad_direct_16', 50: 'wgrad_batched2', 51: 'wgrad_batched',
+                 52: 'wgrad_batched_adam'}
+
 
 class Experts(ctypes.Structure):
     _fields_ = [('mu', c_void_p * MAX_EXPERTS), ('logvar', c_void_p * MAX_EXPERTS)]
@@ -132,6 +147,10 @@ _SIGNATURES = {
     'mvae_convT2d_k4_stats_tiles': (c_size_t, [c_int] * 7),
     'mvae_convT2d_k4_fwd_stats': (c_int, [P, P, P, c_size_t] + [c_int] * 7 + [P, c_size_t, P]),
     'mvae_conv_k4_route': (c_int, [c_int] * 8 + [c_size_t, ctypes.POINTER(c_int)]),
+    'mvae_linear_route': (c_int, [c_int] * 7 + [c_size_t, c_size_t, c_int, c_int, c_int, c_size_t, ctypes.POINTER(c_int),
+                                  ctypes.POINTER(c_int)]),
+    'mvae_linear_wgrad_batched_route': (c_int, [ctypes.POINTER(WgradItem), c_int, c_int, ctypes.POINTER(c_int),
+                                                ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     # K17: the general stride-2 conv family (ks in {4, 5}, pad in {0, 1}, any map size)
     'mvae_conv2d_gen_fwd': (c_int, [P, P, P, P] + [c_int] * 8 + [P]),
     'mvae_conv2d_gen_dgrad': (c_int, [P, P, P, P] + [c_int] * 8 + [P, c_size_t, P]),

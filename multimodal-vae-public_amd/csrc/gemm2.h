@@ -714,14 +714,27 @@ void gemm2s_kernel(const float *__restrict__ P, int ldp, size_t p_cs, const floa
 #define MVAE_G2S_STAGES 4
 #endif
 
+// Which instantiation a plan of gemm_core.h's small layouts (pl.bk == 64) takes here, G2S_NONE when there is none:
+// launch_gemm2s switches on it, the host-only route queries (mvae_linear_route) report it.
+enum G2sTile { G2S_NONE = 0, G2S_32x64_K4, G2S_64x32_K4, G2S_32x64_K2, G2S_64x32_K2, G2S_32x32_K8, G2S_32x32_K4 };
+inline G2sTile g2s_tile(const Plan &pl, int K) {
+    if (pl.bk != 64 || pl.splits != 1 || (K & 3)) return G2S_NONE;
+#ifdef MVAE_TUNING
+    if (getenv("MVAE_G2S_OFF")) return G2S_NONE;
+#endif
+    if (pl.wgm == 1 && pl.wgn == 2 && pl.kw == 4) return G2S_32x64_K4;
+    if (pl.wgm == 2 && pl.wgn == 1 && pl.kw == 4) return G2S_64x32_K4;
+    if (pl.wgm == 1 && pl.wgn == 2 && pl.kw == 2) return G2S_32x64_K2;
+    if (pl.wgm == 2 && pl.wgn == 1 && pl.kw == 2) return G2S_64x32_K2;
+    if (pl.wgm == 1 && pl.wgn == 1 && pl.kw == 8) return G2S_32x32_K8;
+    if (pl.wgm == 1 && pl.wgn == 1 && pl.kw == 4) return G2S_32x32_K4;
+    return G2S_NONE;
+}
+
 // Launch for a plan of gemm_core.h's small layouts (pl.bk == 64): false when the shape has no instantiation here.
 template <class E, bool Q_RK>
 bool launch_gemm2s(const Plan &pl, const float *P, int ldp, size_t p_cs, const float *Q, int ldq, size_t q_cs, E e, int I,
                    int J, int K, int ncls, hipStream_t st, int *status) {
-    if (pl.bk != 64 || pl.splits != 1 || (K & 3)) return false;
-#ifdef MVAE_TUNING
-    if (getenv("MVAE_G2S_OFF")) return false;
-#endif
 #define MVAE_G2S_LAUNCH(TMW, TNW, KW, CH)                                                                         \
     {                                                                                                             \
         constexpr int BM = 32 * TMW, BN = 32 * TNW, BK = 8 * KW * CH, NT = 64 * TMW * TNW * KW, STG = MVAE_G2S_STAGES; \
@@ -739,12 +752,15 @@ bool launch_gemm2s(const Plan &pl, const float *P, int ldp, size_t p_cs, const f
         *status = mvae_launch_status();                                                                           \
         return true;                                                                                              \
     }
-    if (pl.wgm == 1 && pl.wgn == 2 && pl.kw == 4) MVAE_G2S_LAUNCH(1, 2, 4, 1)
-    if (pl.wgm == 2 && pl.wgn == 1 && pl.kw == 4) MVAE_G2S_LAUNCH(2, 1, 4, 1)
-    if (pl.wgm == 1 && pl.wgn == 2 && pl.kw == 2) MVAE_G2S_LAUNCH(1, 2, 2, 2)
-    if (pl.wgm == 2 && pl.wgn == 1 && pl.kw == 2) MVAE_G2S_LAUNCH(2, 1, 2, 2)
-    if (pl.wgm == 1 && pl.wgn == 1 && pl.kw == 8) MVAE_G2S_LAUNCH(1, 1, 8, 1)
-    if (pl.wgm == 1 && pl.wgn == 1 && pl.kw == 4) MVAE_G2S_LAUNCH(1, 1, 4, 2)
+    switch (g2s_tile(pl, K)) {
+        case G2S_32x64_K4: MVAE_G2S_LAUNCH(1, 2, 4, 1)
+        case G2S_64x32_K4: MVAE_G2S_LAUNCH(2, 1, 4, 1)
+        case G2S_32x64_K2: MVAE_G2S_LAUNCH(1, 2, 2, 2)
+        case G2S_64x32_K2: MVAE_G2S_LAUNCH(2, 1, 2, 2)
+        case G2S_32x32_K8: MVAE_G2S_LAUNCH(1, 1, 8, 1)
+        case G2S_32x32_K4: MVAE_G2S_LAUNCH(1, 1, 4, 2)
+        default: break;
+    }
 #undef MVAE_G2S_LAUNCH
     return false;
 }

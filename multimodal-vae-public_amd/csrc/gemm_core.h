@@ -1656,6 +1656,32 @@ inline Plan make_plan(int I, int J, int K, bool allow_split, PlanKind kind = PLA
     return p;
 }
 
+// Which instantiation a plan takes and which launch sums its partials: launch_igemm_impl switches on these two, the
+// host-only route queries (mvae_linear_route) report them.  `small`: the caller has BK = 64 loaders.
+enum IgemmTile { IG_BAD = 0, IG_S64x32_K4, IG_S64x32_K2, IG_S32x64_K4, IG_S32x64_K2, IG_S32x32_K8, IG_S32x32_K4,
+                 IG_32x128, IG_128x128, IG_128x64, IG_64x128, IG_64x64_K4, IG_64x64_K2, IG_64x64 };
+inline IgemmTile igemm_tile(const Plan &pl, bool small) {
+    if (small && pl.bk == 64) {
+        if (pl.wgm == 2 && pl.kw == 4) return IG_S64x32_K4;
+        if (pl.wgm == 2) return IG_S64x32_K2;
+        if (pl.wgn == 2 && pl.kw == 4) return IG_S32x64_K4;
+        if (pl.wgn == 2) return IG_S32x64_K2;
+        return pl.kw == 8 ? IG_S32x32_K8 : IG_S32x32_K4;
+    }
+    if (pl.bk != BK) return IG_BAD;
+    if (pl.wgn == 4) return IG_32x128;
+    if (pl.wm == 2 && pl.wn == 2) return IG_128x128;
+    if (pl.wm == 2 && pl.wn == 1) return IG_128x64;
+    if (pl.wm == 1 && pl.wn == 2) return IG_64x128;
+    return pl.kw == 4 ? IG_64x64_K4 : (pl.kw == 2 ? IG_64x64_K2 : IG_64x64);
+}
+enum SplitFinish { FIN_NONE = 0, FIN_FINISH = 1, FIN_FEW = 2, FIN_FEW_VEC = 3, FIN_G2 = 4 };
+inline SplitFinish igemm_finish(const Plan &pl, int J, const SplitSink &sink) {
+    if (pl.splits <= 1) return FIN_NONE;
+    if (pl.splits > 16) return FIN_FINISH;
+    return (J % 4 == 0 && sink.stride % 4 == 0 && aligned16(sink.ws)) ? FIN_FEW_VEC : FIN_FEW;
+}
+
 // PL / QL: loader templates of the BK = 32 layouts; PS / QS: their BK = 64 versions for the small
 // layouts (SMALL = false: the caller has none -- the conv forms -- and the plan never asks for one).
 template <template <int> class PL, template <int> class QL, class E, bool ROWSUM, bool SMALL,
@@ -1701,41 +1727,48 @@ int launch_igemm_impl(Plan pl, PF make_p, QF make_q, E e, int I, int J, int K, S
         MVAE_GRID_REPORT(kern, grid, NT, lds, I, J, K, sink.items, TM, TN)                               \
         hipLaunchKernelGGL(kern, grid, dim3(NT), lds, st, p, q, e, K, pl.klen, sink);            \
     }
-    bool launched = false;
+    const IgemmTile tile = igemm_tile(pl, SMALL);
+    if (tile == IG_BAD) return MVAE_ERR_ARG;
     if constexpr (SMALL) {
-        if (pl.bk == 64) {
-            launched = true;
-            if (pl.wgm == 2 && pl.kw == 4) MVAE_LAUNCH(PS, QS, 1, 1, 4, 2, 1)
-            else if (pl.wgm == 2) MVAE_LAUNCH(PS, QS, 1, 1, 2, 2, 1)
-            else if (pl.wgn == 2 && pl.kw == 4) MVAE_LAUNCH(PS, QS, 1, 1, 4, 1, 2)
-            else if (pl.wgn == 2) MVAE_LAUNCH(PS, QS, 1, 1, 2, 1, 2)
-            else if (pl.kw == 8) MVAE_LAUNCH(PS, QS, 1, 1, 8, 1, 1)
-            else MVAE_LAUNCH(PS, QS, 1, 1, 4, 1, 1)
+        switch (tile) {
+            case IG_S64x32_K4: MVAE_LAUNCH(PS, QS, 1, 1, 4, 2, 1) break;
+            case IG_S64x32_K2: MVAE_LAUNCH(PS, QS, 1, 1, 2, 2, 1) break;
+            case IG_S32x64_K4: MVAE_LAUNCH(PS, QS, 1, 1, 4, 1, 2) break;
+            case IG_S32x64_K2: MVAE_LAUNCH(PS, QS, 1, 1, 2, 1, 2) break;
+            case IG_S32x32_K8: MVAE_LAUNCH(PS, QS, 1, 1, 8, 1, 1) break;
+            case IG_S32x32_K4: MVAE_LAUNCH(PS, QS, 1, 1, 4, 1, 1) break;
+            default: break;
         }
     }
-    if (!launched) {
-        if (pl.bk != BK) return MVAE_ERR_ARG;
-        if (pl.wgn == 4) MVAE_LAUNCH(PL, QL, 1, 1, 1, 1, 4)
-        else if (pl.wm == 2 && pl.wn == 2) MVAE_LAUNCH(PL, QL, 2, 2, 1, 2, 2)
-        else if (pl.wm == 2 && pl.wn == 1) MVAE_LAUNCH(PL, QL, 2, 1, 1, 2, 2)
-        else if (pl.wm == 1 && pl.wn == 2) MVAE_LAUNCH(PL, QL, 1, 2, 1, 2, 2)
-        else if (pl.kw == 4) MVAE_LAUNCH(PL, QL, 1, 1, 4, 2, 2)
-        else if (pl.kw == 2) MVAE_LAUNCH(PL, QL, 1, 1, 2, 2, 2)
-        else MVAE_LAUNCH(PL, QL, 1, 1, 1, 2, 2)
+    switch (tile) {
+        case IG_32x128: MVAE_LAUNCH(PL, QL, 1, 1, 1, 1, 4) break;
+        case IG_128x128: MVAE_LAUNCH(PL, QL, 2, 2, 1, 2, 2) break;
+        case IG_128x64: MVAE_LAUNCH(PL, QL, 2, 1, 1, 2, 2) break;
+        case IG_64x128: MVAE_LAUNCH(PL, QL, 1, 2, 1, 2, 2) break;
+        case IG_64x64_K4: MVAE_LAUNCH(PL, QL, 1, 1, 4, 2, 2) break;
+        case IG_64x64_K2: MVAE_LAUNCH(PL, QL, 1, 1, 2, 2, 2) break;
+        case IG_64x64: MVAE_LAUNCH(PL, QL, 1, 1, 1, 2, 2) break;
+        default: break;
     }
 #undef MVAE_LAUNCH
-    if (pl.splits > 1) {
-        if (pl.splits > 16) {
+    switch (igemm_finish(pl, J, sink)) {
+        case FIN_FINISH: {
             dim3 grid((J + 31) / 32, I, sink.ncls);
             hipLaunchKernelGGL((finish_kernel<E>), grid, dim3(256), 0, st, sink, pl.splits, e);
-        } else if (J % 4 == 0 && sink.stride % 4 == 0 && aligned16(sink.ws)) {
+            break;
+        }
+        case FIN_FEW_VEC: {
             const size_t nvec = (size_t)I * (J / 4) + (sink.rowsum_final ? I : 0);
             hipLaunchKernelGGL((finish_few_vec_kernel<E>), dim3((unsigned)((nvec + 255) / 256), sink.ncls), dim3(256), 0, st, sink,
                                pl.splits, e);
-        } else {
+            break;
+        }
+        case FIN_FEW: {
             dim3 grid((J + 255) / 256, I, sink.ncls);
             hipLaunchKernelGGL((finish_few_kernel<E>), grid, dim3(256), 0, st, sink, pl.splits, e);
+            break;
         }
+        default: break;
     }
     return mvae_launch_status();
 }

@@ -459,20 +459,21 @@ __global__ __launch_bounds__(64 * KW) void wgrad_batched2_kernel(WgradBatch2Args
     wgrad_tile2<KW, FM, FN, PD>(w, tile_i, tile_j);
 }
 
-// Re-tile the table for FM x FN wave tiles, cut it into XCD segments, launch.  Returns false when the batch has an
-// item the v2 tile code does not take (none today: kept for the Adam-fused form, which stays on the old kernel).
-inline bool wgrad_batched2_launch(const WgradBatchArgs &a, hipStream_t st, int *status) {
+struct Wgrad2Route { bool ok; int shape, kw; };      // shape: 22 = 64 x 64 wave tiles, 21 = 64 x 32, 11 = 32 x 32
+// (wgrad_batched2_launch switches on it, mvae_linear_wgrad_batched_route reports it)
+inline Wgrad2Route wgrad_batched2_route(const WgradBatchArgs &a) {
+    Wgrad2Route none = {false, 0, 0};
     long t22 = 0, t21 = 0, t11 = 0;
     int max_m = 0;
     for (int q = 0; q < a.n; ++q) {
         const WgradBatchItem &w = a.it[q];
-        if (!w.dy) return false;
+        if (!w.dy) return none;
         t22 += cdiv(w.I, 64) * cdiv(w.J, 64); t21 += cdiv(w.I, 64) * cdiv(w.J, 32); t11 += cdiv(w.I, 32) * cdiv(w.J, 32);
         if (w.M > max_m) max_m = w.M;
         // byte offsets of (surplus) chunks stay below 2^31 (signed in wb2_rsrc): with KW waves per tile and PD register sets
         // the prefetch runs up to 8 * KW * (3 * PD + 1) rows past the batch -- KW <= 16, PD <= 2 (8 * 16 * 5 was short)
         const long over = (long)w.M + 8 * 16 * 8;
-        if (over * w.lddy * 4 >= (1L << 31) || over * w.ldx * 4 >= (1L << 31)) return false;
+        if (over * w.lddy * 4 >= (1L << 31) || over * w.ldx * 4 >= (1L << 31)) return none;
     }
     // Wave tile: every tile of a launch costs the same (M rows x tile area), blocks spread evenly over the 256 CUs, and the
     // launch lasts as long as its busiest CU -- ceil(tiles / 256) tiles of FM x FN MFMAs per 8 rows.  Pick the shape with
@@ -485,12 +486,22 @@ inline bool wgrad_batched2_launch(const WgradBatchArgs &a, hipStream_t st, int *
     if (busy21 < busy) { shape = 21; busy = busy21; }
     if (busy11 < busy) { shape = 11; busy = busy11; }
     const long tiles = shape == 22 ? t22 : (shape == 21 ? t21 : t11);
-    const int fm = shape == 11 ? 1 : 2, fn = shape == 22 ? 2 : 1;
     // waves per tile (they split the batch rows): ~2 per SIMD over the launch, at least 4 chunks of 8 rows each
     int kw = tiles >= 1024 ? 2 : (tiles >= 400 ? 4 : (tiles >= 160 ? 8 : 16));
     if (shape == 22 && kw < 4) kw = 4;
     while (kw > 2 && max_m < 8 * 4 * kw) kw >>= 1;
     if (shape == 11 && kw < 4) kw = 4;
+    // the instantiations there are: 64 x 64 and 32 x 32 tiles with 4, 8 or 16 waves, 64 x 32 with 2, 4, 8 or 16
+    if (kw >= 16) kw = 16;
+    else if (kw != 8 && !(kw == 2 && shape == 21)) kw = 4;
+    const Wgrad2Route r = {true, shape, kw};
+    return r;
+}
+
+// Re-tile the table for the FM x FN wave tiles of the route, cut it into XCD segments, launch.
+inline int wgrad_batched2_launch(const WgradBatchArgs &a, const Wgrad2Route &r, hipStream_t st) {
+    const int shape = r.shape, kw = r.kw;
+    const int fm = shape == 11 ? 1 : 2, fn = shape == 22 ? 2 : 1;
     WgradBatch2Args b;
     b.n = a.n;
     int total = 0;
@@ -516,15 +527,14 @@ inline bool wgrad_batched2_launch(const WgradBatchArgs &a, hipStream_t st, int *
         hipLaunchKernelGGL(kern, grid, dim3(64 * KWV), lds, st, b);                                           \
     }
     if (shape == 22) {
-        if (kw >= 16) MVAE_WB2(16, 2, 2, 1) else if (kw == 8) MVAE_WB2(8, 2, 2, MVAE_WB2_PD22) else MVAE_WB2(4, 2, 2, MVAE_WB2_PD22)
+        if (kw == 16) MVAE_WB2(16, 2, 2, 1) else if (kw == 8) MVAE_WB2(8, 2, 2, MVAE_WB2_PD22) else MVAE_WB2(4, 2, 2, MVAE_WB2_PD22)
     } else if (shape == 21) {
-        if (kw >= 16) MVAE_WB2(16, 2, 1, 2) else if (kw == 8) MVAE_WB2(8, 2, 1, 2) else if (kw == 4) MVAE_WB2(4, 2, 1, 3) else MVAE_WB2(2, 2, 1, 3)
+        if (kw == 16) MVAE_WB2(16, 2, 1, 2) else if (kw == 8) MVAE_WB2(8, 2, 1, 2) else if (kw == 4) MVAE_WB2(4, 2, 1, 3) else MVAE_WB2(2, 2, 1, 3)
     } else {
-        if (kw >= 16) MVAE_WB2(16, 1, 1, MVAE_WB2_PD11) else if (kw == 8) MVAE_WB2(8, 1, 1, MVAE_WB2_PD11) else MVAE_WB2(4, 1, 1, MVAE_WB2_PD11)
+        if (kw == 16) MVAE_WB2(16, 1, 1, MVAE_WB2_PD11) else if (kw == 8) MVAE_WB2(8, 1, 1, MVAE_WB2_PD11) else MVAE_WB2(4, 1, 1, MVAE_WB2_PD11)
     }
 #undef MVAE_WB2
-    *status = mvae_launch_status();
-    return true;
+    return mvae_launch_status();
 }
 
 // shapes the direct tile code serves well on its own merits (32-bit byte offsets inside the operands included)
@@ -533,14 +543,32 @@ inline bool wgrad_batch_item_ok(int I, int J, int M, int lddy, int ldx) {
     return tiles <= 2048 && M <= 4096 && (long)M * lddy * 4 < (1L << 32) && (long)M * ldx * 4 < (1L << 32);
 }
 
-inline int wgrad_batched_launch(WgradBatchArgs &a, hipStream_t st, const AdamFuse *adam = nullptr) {
-    if (!adam) {
-        int status = MVAE_OK;
-        if (wgrad_batched2_launch(a, st, &status)) return status;
+// waves per tile of the 32 x 32 kernels: enough blocks x waves to put ~4 waves on every SIMD, a reduction slice of >= 4
+// chunks each
+inline int wgrad_batched_waves(int total) { return total >= 768 ? 4 : (total >= 256 ? 8 : 16); }
+
+// Which kernel a batch takes (wgrad_batched_launch switches on it, mvae_linear_wgrad_batched_route reports it): the
+// wave-tile kernel unless the batch carries the Adam update or has an item that kernel does not take.
+struct WgradBatchRoute { int route, tile_m, tile_n, waves; Wgrad2Route r2; };
+inline WgradBatchRoute wgrad_batched_route(const WgradBatchArgs &a, bool adam) {
+    WgradBatchRoute r;
+    r.r2.ok = false; r.r2.shape = 0; r.r2.kw = 0;
+    if (!adam) r.r2 = wgrad_batched2_route(a);
+    if (r.r2.ok) {
+        r.route = MVAE_LROUTE_WGRAD_BATCHED2;
+        r.tile_m = r.r2.shape == 11 ? 32 : 64; r.tile_n = r.r2.shape == 22 ? 64 : 32; r.waves = r.r2.kw;
+    } else {
+        r.route = adam ? MVAE_LROUTE_WGRAD_BATCHED_ADAM : MVAE_LROUTE_WGRAD_BATCHED;
+        r.tile_m = r.tile_n = 32; r.waves = wgrad_batched_waves(a.it[a.n - 1].tile_end);
     }
+    return r;
+}
+
+inline int wgrad_batched_launch(WgradBatchArgs &a, hipStream_t st, const AdamFuse *adam = nullptr) {
+    const WgradBatchRoute r = wgrad_batched_route(a, adam != nullptr);
+    if (r.route == MVAE_LROUTE_WGRAD_BATCHED2) return wgrad_batched2_launch(a, r.r2, st);
     const int total = a.it[a.n - 1].tile_end;
-    // waves per tile: enough blocks x waves to put ~4 waves on every SIMD, a reduction slice of >= 4 chunks each
-    const int kw = total >= 768 ? 4 : (total >= 256 ? 8 : 16);
+    const int kw = r.waves;
 #define MVAE_WB(KWV)                                                                                          \
     {                                                                                                         \
         constexpr size_t lds = ((size_t)KWV * 32 * 33 + (size_t)KWV * 64) * sizeof(float);                    \
@@ -576,12 +604,17 @@ inline bool wgrad_direct_ok(int I, int J, int M) {
     return tiles >= 16 && tiles <= 2048 && M <= 4096;
 }
 
+inline int wgrad_direct_waves(long tiles) {
+    int kw = tiles >= 192 ? 4 : (tiles >= 96 ? 8 : 16);
+    if (MVAE_TUNE(small_waves)) kw = MVAE_TUNE(small_waves);
+    return kw == 4 || kw == 8 ? kw : 16;        // the instantiations there are
+}
+
 inline int wgrad_direct_launch(const float *dy, int lddy, const float *x, int ldx, EpRowMajor e, int I, int J, int M,
                                float *db, int db_accumulate, hipStream_t st) {
     const long tiles = cdiv(I, 32) * cdiv(J, 32);
     const dim3 grid((unsigned)cdiv(J, 32), (unsigned)cdiv(I, 32));
-    int kw = tiles >= 192 ? 4 : (tiles >= 96 ? 8 : 16);
-    if (MVAE_TUNE(small_waves)) kw = MVAE_TUNE(small_waves);
+    const int kw = wgrad_direct_waves(tiles);
 #define MVAE_WD(RS, KWV)                                                                                      \
     {                                                                                                         \
         constexpr size_t lds = ((size_t)KWV * 32 * 33 + (size_t)KWV * 64) * sizeof(float);                    \

@@ -167,6 +167,58 @@ def linear_wgrad_batched(items, adam=None):
             check(_lib.lib().mvae_linear_wgrad_batched(arr, len(chunk), _stream()), 'mvae_linear_wgrad_batched')
 
 
+def linear_route(op, M, N, K, G=1, ld_a=None, ld_b=None, gs_a=None, gs_b=None, aligned=True, form='other', db=False,
+                 ws_bytes=None):
+    """(route, splits, finish) of the Linear launch ``op`` (a key of ``_lib.LINEAR_OPS``) on M rows, N output and K input
+    features -- the name of the kernel instantiation it takes (``_lib.LINEAR_ROUTES``), the number of partials of a split
+    reduction (1: none) and the launch that sums them (``_lib.LINEAR_FINISH``, None: none).  Host only
+    (mvae_linear_route: the route function the launch itself switches on).  ``ld_a``, ``ld_b``: the launch's two leading
+    dimensions in the order of its argument list (default: dense); ``gs_a``, ``gs_b``: the group strides of its two input
+    operands (default: dense [G, rows, width] activations, dense weights); ``aligned``: the input operands are 16-byte
+    aligned; ``form`` (forward): 'pre+act', 'act' (no mask) or 'other'; ``db`` (weight gradient): with a bias gradient;
+    ``ws_bytes``: the scratch the launch gets, by default what the wrappers here pass before anything asked for more
+    (``_WS_MIN_BYTES``), 0 for none.  Raises where the launch would refuse the arguments."""
+    dense = {'fwd': (K, N, M * K, N * K), 'bce_fwd': (K, N, 0, 0), 'ce_fwd': (K, N, 0, 0),
+             'dgrad': (N, K, M * N, N * K), 'wgrad': (N, K, M * N, M * K)}[op]
+    ld_a, ld_b, gs_a, gs_b = (d if v is None else v for v, d in zip((ld_a, ld_b, gs_a, gs_b), dense))
+    sp, fin = ctypes.c_int(1), ctypes.c_int(0)
+    rc = _lib.lib().mvae_linear_route(_lib.LINEAR_OPS[op], G, M, N, K, ld_a, ld_b, gs_a, gs_b, 1 if aligned else 0,
+                                      _lib.LINEAR_FORMS[form], 1 if db else 0,
+                                      _WS_MIN_BYTES if ws_bytes is None else int(ws_bytes), ctypes.byref(sp),
+                                      ctypes.byref(fin))
+    if rc <= 0:
+        check(rc if rc < 0 else -1, 'mvae_linear_route')
+    return _lib.LINEAR_ROUTES[rc], sp.value, _lib.LINEAR_FINISH[fin.value]
+
+
+def linear_wgrad_batched_route(items, adam=False):
+    """(route, (tile rows, tile columns), waves per tile) of one batched weight-gradient launch.  ``items``: tensors as for
+    ``linear_wgrad_batched`` (on any device: nothing is read), or plain (M, N, K, lddy, ldx, with_db, accumulate) tuples;
+    at most WGRAD_BATCH_MAX of them.  Host only (mvae_linear_wgrad_batched_route).  Raises where the launch would refuse
+    the table."""
+    items = list(items)
+    arr = (_lib.WgradItem * max(len(items), 1))()
+    for q, it in enumerate(items):
+        if len(it) == 7:      # stand-in pointers: distinct, 16-byte aligned, never dereferenced
+            M, N, K, lddy, ldx, with_db, acc = it
+            base = (q + 1) << 24
+            arr[q] = _lib.WgradItem(base, lddy, base + 16, ldx, base + 32, base + 48 if with_db else None, M, N, K,
+                                    ACCUMULATE if acc else 0)
+        else:
+            dy, x, dw, db, acc = it
+            if dy is None:
+                arr[q] = _lib.WgradItem(None, 0, None, 0, _ptr(dw), None, 0, 0, dw.numel(), 0)
+            else:
+                arr[q] = _lib.WgradItem(_ptr(dy), dy.stride(0), _ptr(x), x.stride(0), _ptr(dw), _ptr(db), dy.shape[0],
+                                        dy.shape[1], x.shape[1], ACCUMULATE if acc else 0)
+    tm, tn, kw = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    rc = _lib.lib().mvae_linear_wgrad_batched_route(arr, len(items), 1 if adam else 0, ctypes.byref(tm), ctypes.byref(tn),
+                                                    ctypes.byref(kw))
+    if rc <= 0:
+        check(rc if rc < 0 else -1, 'mvae_linear_wgrad_batched_route')
+    return _lib.LINEAR_ROUTES[rc], (tm.value, tn.value), kw.value
+
+
 # ---------------------------------------------------------------------------- grouped Linear
 # G problems of one shape per launch: activations are [G, rows, width] tensors, parameters are
 # (tensor of group 0, stride in floats to the same tensor of the next group) -- the experts' slices

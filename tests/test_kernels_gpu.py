@@ -39,6 +39,12 @@ def swish_grad(x):
 
 
 # ----------------------------------------------------------------------------- Linear
+# These shapes, GROUPED_SHAPES, the pair shapes and the batches below reach a part of the kernel instantiations the Linear
+# launches choose between (by kernels.linear_route: 8 of the forward's routes, 8 of the data gradient's, 8 of the weight
+# gradient's, 3 of the 9 reachable wgrad_batched2_kernel forms).  They do NOT reach gemm2s 32 x 64 / 2 k-groups and
+# 32 x 32 / 4 k-groups, the narrow 32 x 128 plan with float4 loaders, 64 x 64 tiles with 2 k-groups, most split / finish
+# combinations, wgrad_direct_kernel with 8 waves or four of the small layouts under a weight gradient:
+# tests/test_linear_routes_gpu.py runs every reachable route, each case asserting through the query which kernel it is on.
 LIN_SHAPES = [(128, 512, 784), (512, 128, 512), (37, 10, 512), (256, 512, 18), (300, 1, 512),
               (64, 200, 6400), (1024, 6272, 512), (130, 100, 200), (3, 5, 7),
               # the MNIST step's shapes at batch 512 (rows of two ELBO terms = 1024): these run on the small
