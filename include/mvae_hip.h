@@ -709,6 +709,39 @@ int mvae_copy2d(const float *src, int lds, float *dst, int ldd, const float *mas
 int mvae_argmax_rows(const float *x, int ldx, int64_t *out, int R, int K, mvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * K18  The whole greedy TextDecoder after z2h in one launch per direction (csrc/gru_seq.hip).  A workgroup owns 16
+ *      batch rows for all L steps of both GRU layers, the h2o Linear and the arg-max feedback; workgroups never
+ *      communicate (no grid barrier, flag or atomic).  All buffers are contiguous fp32 (fed: int64), weights in
+ *      nn.GRU / nn.Linear layout: w_ih0 [3H, H+D], w_hh0 / w_ih1 / w_hh1 [3H, H], w_h2o [n_chars, H+D].
+ *   gru_dec_seq_supported  host-only: 1 where the kernels' LDS plan holds (both fit the CU's 160 KiB; n_chars <= 16;
+ *                 H, D, L <= 4096; B * 4H and B * (H+D) below 2^31), else 0.  H and D need no alignment.
+ *   gru_dec_seq_fwd  z [B, D], hz = z2h(z) [B, H] -> words [B, L, n_chars]; masks (nullable) [L, B, H] in {0, 1}, the
+ *                 layer-0 output is multiplied by mask * mask_scale.  The tape (all seven pointers, or none of them)
+ *                 is time-major: xcat_all, ocat_all [L, B, H+D]; h0_all, h1_all [L+1, B, H] (slot 0 = hz);
+ *                 d0_all [L, B, H]; gates0, gates1 [L, B, 4H] (r | z | n | gh_n).  fed (nullable) [L, B]: the
+ *                 characters fed in, fed[0] = sos.  Character indices are clamped to [0, n_chars).
+ *   gru_dec_seq_bwd  dwords [B, L, n_chars] and the tape -> dgi0/dgh0/dgi1/dgh1_all [L, B, 3H], demb_all [L, B, H]
+ *                 (gradient of swish(embed)), dlog_all [L, B, n_chars] (dwords time-major), dhz [B, H], dz [B, D]
+ *                 (the direct paths only; the caller adds dhz . W_z2h).  No weight gradients: those are Linear
+ *                 weight-gradient launches on the [L * B, .] views.
+ *   Both return MVAE_ERR_ARG before any launch on a null pointer, B <= 0 or an unsupported geometry.
+ * ------------------------------------------------------------------------------------ */
+int mvae_gru_dec_seq_supported(int B, int H, int D, int n_chars, int L);
+int mvae_gru_dec_seq_fwd(const float *z, const float *hz, const float *w_emb, const float *w_ih0, const float *w_hh0,
+                         const float *b_ih0, const float *b_hh0, const float *w_ih1, const float *w_hh1,
+                         const float *b_ih1, const float *b_hh1, const float *w_h2o, const float *b_h2o,
+                         const float *masks /* nullable */, float mask_scale, float *words, float *xcat_all,
+                         float *h0_all, float *h1_all, float *d0_all, float *ocat_all, float *gates0, float *gates1,
+                         int64_t *fed /* nullable */, int B, int H, int D, int n_chars, int L, int sos,
+                         mvae_stream_t stream);
+int mvae_gru_dec_seq_bwd(const float *dwords, const float *w_ih0, const float *w_hh0, const float *w_ih1,
+                         const float *w_hh1, const float *w_h2o, const float *masks /* nullable */, float mask_scale,
+                         const float *h0_all, const float *h1_all, const float *gates0, const float *gates1,
+                         float *dgi0_all, float *dgh0_all, float *dgi1_all, float *dgh1_all, float *demb_all,
+                         float *dlog_all, float *dhz, float *dz, int B, int H, int D, int n_chars, int L,
+                         mvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * C1  Gradient exchange of data-parallel replicas -- RCCL over xGMI.
  *     The reference has NO counterpart: it is single-process, single-device (no DataParallel, no
  *     torch.distributed anywhere; README.md:47 `CUDA_VISIBLE_DEVICES=0`).  What this replaces is what N

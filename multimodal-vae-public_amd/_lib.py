@@ -193,6 +193,10 @@ _SIGNATURES = {
     'mvae_embedding_bwd': (c_int, [P, c_int, P, P, c_int, P, c_int, c_int, c_int, c_int, P]),
     'mvae_copy2d': (c_int, [P, c_int, P, c_int, P, c_int, c_float, c_int, c_int, c_int, P]),
     'mvae_argmax_rows': (c_int, [P, c_int, P, c_int, c_int, P]),
+    # K18: the whole greedy TextDecoder in one launch per direction
+    'mvae_gru_dec_seq_supported': (c_int, [c_int] * 5),
+    'mvae_gru_dec_seq_fwd': (c_int, [P] * 14 + [c_float] + [P] * 9 + [c_int] * 6 + [P]),
+    'mvae_gru_dec_seq_bwd': (c_int, [P] * 7 + [c_float] + [P] * 12 + [c_int] * 5 + [P]),
     # C1: the gradient exchange (RCCL bound at run time)
     'mvae_comm_use_library': (c_int, [ctypes.c_char_p]),
     'mvae_comm_rccl_version': (c_int, []),

@@ -1082,3 +1082,74 @@ def argmax_rows(x, out):
     if not (out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.numel() == R):
         raise RuntimeError('argmax_rows wants a contiguous int64 GPU output of one entry per row')
     check(_lib.lib().mvae_argmax_rows(_ptr(x), x.stride(0), _ptr(out), R, K_, _stream()), 'mvae_argmax_rows')
+
+
+# ---------------------------------------------------------------------------- whole-sequence TextDecoder (MultiMNIST)
+def gru_dec_seq_supported(B, H, D, n_chars, L):
+    """Whether the one-launch decoder kernels take this geometry (host-only query, no GPU needed)."""
+    return bool(_lib.lib().mvae_gru_dec_seq_supported(int(B), int(H), int(D), int(n_chars), int(L)))
+
+
+def _shaped(t, shape, what, dtype=torch.float32):
+    if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise RuntimeError('%s must be a contiguous %s GPU tensor of shape %s (got %s %s)'
+                           % (what, dtype, tuple(shape), t.dtype, tuple(t.shape)))
+    return t
+
+
+def _dec_weights(w_emb, p0, p1, w_h2o, b_h2o, H, D, n_chars):
+    _shaped(w_emb, (n_chars, H), 'embed.weight')
+    for (w_ih, w_hh, b_ih, b_hh), kx, l in ((p0, H + D, 0), (p1, H, 1)):
+        _shaped(w_ih, (3 * H, kx), 'weight_ih_l%d' % l); _shaped(w_hh, (3 * H, H), 'weight_hh_l%d' % l)
+        _shaped(b_ih, (3 * H,), 'bias_ih_l%d' % l); _shaped(b_hh, (3 * H,), 'bias_hh_l%d' % l)
+    _shaped(w_h2o, (n_chars, H + D), 'h2o.weight'); _shaped(b_h2o, (n_chars,), 'h2o.bias')
+
+
+def gru_dec_seq_fwd(z, hz, w_emb, p0, p1, w_h2o, b_h2o, masks, mask_scale, words, tape, fed, sos):
+    """All ``L`` greedy steps of the 2-layer GRU decoder in one launch.  ``p0`` / ``p1`` = (w_ih, w_hh, b_ih, b_hh) of the
+    layers; ``masks`` [L, B, H] or None; ``tape`` = (xcat_all, h0_all, h1_all, d0_all, ocat_all, gates0, gates1) or None;
+    ``fed`` [L, B] int64 or None."""
+    B, D = z.shape
+    H = hz.shape[1]
+    _, L, n_chars = words.shape
+    _shaped(z, (B, D), 'z'); _shaped(hz, (B, H), 'hz'); _shaped(words, (B, L, n_chars), 'words')
+    _dec_weights(w_emb, p0, p1, w_h2o, b_h2o, H, D, n_chars)
+    if masks is not None:
+        _shaped(masks, (L, B, H), 'masks')
+    if tape is not None:
+        for t, shape, what in zip(tape, ((L, B, H + D), (L + 1, B, H), (L + 1, B, H), (L, B, H), (L, B, H + D),
+                                         (L, B, 4 * H), (L, B, 4 * H)),
+                                  ('xcat_all', 'h0_all', 'h1_all', 'd0_all', 'ocat_all', 'gates0', 'gates1')):
+            _shaped(t, shape, what)
+    if fed is not None:
+        _shaped(fed, (L, B), 'fed', torch.int64)
+    tp = [_ptr(t) for t in tape] if tape is not None else [None] * 7
+    check(_lib.lib().mvae_gru_dec_seq_fwd(_ptr(z), _ptr(hz), _ptr(w_emb), _ptr(p0[0]), _ptr(p0[1]), _ptr(p0[2]),
+                                          _ptr(p0[3]), _ptr(p1[0]), _ptr(p1[1]), _ptr(p1[2]), _ptr(p1[3]), _ptr(w_h2o),
+                                          _ptr(b_h2o), _ptr(masks), float(mask_scale), _ptr(words), *tp, _ptr(fed),
+                                          B, H, D, n_chars, L, int(sos), _stream()), 'mvae_gru_dec_seq_fwd')
+
+
+def gru_dec_seq_bwd(dwords, p0, p1, w_h2o, masks, mask_scale, h0_all, h1_all, gates0, gates1, dgi0_all, dgh0_all,
+                    dgi1_all, dgh1_all, demb_all, dlog_all, dhz, dz):
+    """The reverse recurrence of ``gru_dec_seq_fwd`` in one launch: the pre-activation gradients of every step
+    (time-stacked), the embedding and logit gradients, and the direct parts of dhz / dz.  No weight gradients."""
+    B, L, n_chars = dwords.shape
+    H = dhz.shape[1]
+    D = dz.shape[1]
+    _shaped(dwords, (B, L, n_chars), 'dwords'); _shaped(dhz, (B, H), 'dhz'); _shaped(dz, (B, D), 'dz')
+    for (w_ih, w_hh), kx, l in ((p0[:2], H + D, 0), (p1[:2], H, 1)):
+        _shaped(w_ih, (3 * H, kx), 'weight_ih_l%d' % l); _shaped(w_hh, (3 * H, H), 'weight_hh_l%d' % l)
+    _shaped(w_h2o, (n_chars, H + D), 'h2o.weight')
+    if masks is not None:
+        _shaped(masks, (L, B, H), 'masks')
+    _shaped(h0_all, (L + 1, B, H), 'h0_all'); _shaped(h1_all, (L + 1, B, H), 'h1_all')
+    _shaped(gates0, (L, B, 4 * H), 'gates0'); _shaped(gates1, (L, B, 4 * H), 'gates1')
+    for t, what in ((dgi0_all, 'dgi0_all'), (dgh0_all, 'dgh0_all'), (dgi1_all, 'dgi1_all'), (dgh1_all, 'dgh1_all')):
+        _shaped(t, (L, B, 3 * H), what)
+    _shaped(demb_all, (L, B, H), 'demb_all'); _shaped(dlog_all, (L, B, n_chars), 'dlog_all')
+    check(_lib.lib().mvae_gru_dec_seq_bwd(_ptr(dwords), _ptr(p0[0]), _ptr(p0[1]), _ptr(p1[0]), _ptr(p1[1]), _ptr(w_h2o),
+                                          _ptr(masks), float(mask_scale), _ptr(h0_all), _ptr(h1_all), _ptr(gates0),
+                                          _ptr(gates1), _ptr(dgi0_all), _ptr(dgh0_all), _ptr(dgi1_all), _ptr(dgh1_all),
+                                          _ptr(demb_all), _ptr(dlog_all), _ptr(dhz), _ptr(dz), B, H, D, n_chars, L,
+                                          _stream()), 'mvae_gru_dec_seq_bwd')

@@ -23,7 +23,9 @@ column ranges of one buffer), the gate arithmetic / embeddings / arg-max feedbac
 forward and backward are hand-written (``torch.autograd.Function`` shells), no ATen arithmetic.  What the reference
 evaluates but never uses is not evaluated: the backward direction of the encoder's GRU contributes only its FIRST
 step (on the last character) to ``x[-1]`` (:177).  The latent path (PoE, draw, KL) is the fused ``mvae_poe_*`` launch of
-the other four models.  There is no fused or captured MultiMNIST step: ``train.py`` runs the modules eagerly."""
+the other four models.  The decoder's four greedy steps run as one launch per direction (csrc/gru_seq.hip) where
+``TextDecoder.whole_sequence`` is set; the per-cell launches remain as the fallback.  There is no fused or captured
+MultiMNIST step: ``train.py`` runs the modules eagerly."""
 import warnings
 
 import torch
@@ -265,10 +267,74 @@ class _TextDecoderFn(torch.autograd.Function):
         return (dz, None, None, dw_emb, dw_z2h, db_z2h, dw_h2o, db_h2o) + g0 + g1
 
 
+class _TextDecoderSeqFn(torch.autograd.Function):
+    """The decoder on the whole-sequence kernels (csrc/gru_seq.hip): z2h, ONE launch for the four greedy steps of both GRU
+    layers + h2o + arg-max; backward: ONE launch for the reverse recurrence, then the weight gradients as five launches
+    on the time-stacked [L * B, .] tapes.  ``masks`` is one [L, B, H] tensor (or None), ``want_tape`` False under
+    ``no_grad``: nothing but the logits and the fed characters is stored then."""
+    @staticmethod
+    def forward(ctx, z, masks, holder, want_tape, w_emb, w_z2h, b_z2h, w_h2o, b_h2o, *gru_params):
+        z = z.contiguous()
+        B, D = z.shape
+        H = w_emb.shape[1]
+        p0, p1 = gru_params[:4], gru_params[4:8]
+        n_chars, L = w_h2o.shape[0], max_length
+        hz = _new(B, H, like=z)
+        K.linear_fwd(z, w_z2h, b_z2h, hz, None)
+        words = _new(B, L, n_chars, like=z)
+        fed = torch.empty(L, B, dtype=torch.int64, device=z.device)
+        tape = None
+        if want_tape:
+            tape = (_new(L, B, H + D, like=z), _new(L + 1, B, H, like=z), _new(L + 1, B, H, like=z), _new(L, B, H, like=z),
+                    _new(L, B, H + D, like=z), _new(L, B, 4 * H, like=z), _new(L, B, 4 * H, like=z))
+        K.gru_dec_seq_fwd(z, hz, w_emb, p0, p1, w_h2o, b_h2o, masks, 1.0 / KEEP, words, tape, fed, SOS)
+        holder['fed'] = fed
+        ctx.tapes = (z, masks, fed, tape)
+        ctx.params = (w_emb, w_z2h, w_h2o, p0, p1)
+        return words
+
+    @staticmethod
+    def backward(ctx, dwords):
+        z, masks, fed, tape = ctx.tapes
+        if tape is None:
+            raise RuntimeError('TextDecoder: backward through a forward that ran without gradient tracking')
+        xcat_all, h0_all, h1_all, d0_all, ocat_all, gates0, gates1 = tape
+        w_emb, w_z2h, w_h2o, p0, p1 = ctx.params
+        B, D = z.shape
+        H = w_emb.shape[1]
+        n_chars, L = w_h2o.shape[0], max_length
+        dwords = dwords.contiguous()
+        dgi0, dgh0, dgi1, dgh1 = (_new(L, B, 3 * H, like=z) for _ in range(4))
+        demb, dlog = _new(L, B, H, like=z), _new(L, B, n_chars, like=z)
+        dhz, dz = _new(B, H, like=z), _new(B, D, like=z)
+        K.gru_dec_seq_bwd(dwords, p0, p1, w_h2o, masks, 1.0 / KEEP, h0_all, h1_all, gates0, gates1, dgi0, dgh0, dgi1, dgh1,
+                          demb, dlog, dhz, dz)
+        g0 = tuple(torch.empty_like(p) for p in p0)
+        g1 = tuple(torch.empty_like(p) for p in p1)
+        R = L * B
+        K.linear_wgrad(dgi0.view(R, 3 * H), xcat_all.view(R, H + D), g0[0], g0[2])
+        K.linear_wgrad(dgh0.view(R, 3 * H), h0_all[:L].view(R, H), g0[1], g0[3])       # h_prev of step i = slot i
+        K.linear_wgrad(dgi1.view(R, 3 * H), d0_all.view(R, H), g1[0], g1[2])
+        K.linear_wgrad(dgh1.view(R, 3 * H), h1_all[:L].view(R, H), g1[1], g1[3])
+        dw_h2o, db_h2o = torch.empty_like(w_h2o), _new(n_chars, like=z)
+        K.linear_wgrad(dlog.view(R, n_chars), ocat_all.view(R, H + D), dw_h2o, db_h2o)
+        dw_emb = torch.empty_like(w_emb)
+        K.embedding_bwd(fed.view(R), w_emb, demb.view(R, H), dw_emb, swish=True)
+        dw_z2h, db_z2h = torch.empty_like(w_z2h), _new(w_z2h.shape[0], like=z)
+        K.linear_wgrad(dhz, z, dw_z2h, db_z2h)
+        K.linear_dgrad(dhz, w_z2h, dz, accumulate=True)
+        ctx.tapes = None
+        return (dz, None, None, None, dw_emb, dw_z2h, db_z2h, dw_h2o, db_h2o) + g0 + g1
+
+
 class TextDecoder(nn.Module):
     """Parametrizes p(y|z) (multimnist/model.py:182-228).  ``forward(z)`` returns the [batch, 4, n_characters] logits;
     ``dropout_masks`` (4 tensors [batch, 200] in {0, 1}) replays a host draw in parity runs, otherwise the training-mode
-    masks come from the device Philox stream.  ``last_fed`` holds the characters fed back ([4, batch])."""
+    masks come from the device Philox stream.  ``last_fed`` holds the characters fed back ([4, batch]).
+    ``whole_sequence`` (an attribute, not a constructor argument) selects the one-launch kernels of csrc/gru_seq.hip
+    where ``kernels.gru_dec_seq_supported`` takes the geometry; False runs the per-cell launches."""
+    WHOLE_SEQUENCE_DEFAULT = True       # profiles/multimnist_gru_seq.txt
+
     def __init__(self, n_latents, n_characters, n_hiddens=200):
         super().__init__()
         self.embed = nn.Embedding(n_characters, n_hiddens)
@@ -279,31 +345,47 @@ class TextDecoder(nn.Module):
         self.n_characters = n_characters
         self.n_hiddens = n_hiddens
         self.last_fed = None
+        self.whole_sequence = self.WHOLE_SEQUENCE_DEFAULT
         self.__dict__['_rng'] = None
 
     def seed_noise(self, seed):
         self.__dict__['_rng'] = (int(seed), torch.zeros(1, dtype=torch.int64, device=self.embed.weight.device))
 
-    def _device_masks(self, B):
+    def _device_mask_tensor(self, B):
         st = self.__dict__.get('_rng')
         if st is None or st[1].device != self.embed.weight.device:
             self.seed_noise(0x5DEECE66D)
             st = self.__dict__['_rng']
         masks = torch.empty(max_length, B, self.n_hiddens, dtype=torch.float32, device=self.embed.weight.device)
         K.bernoulli_(masks, KEEP, st[0], st[1])
+        return masks
+
+    def _device_masks(self, B):
+        masks = self._device_mask_tensor(B)
         return [masks[i] for i in range(max_length)]
 
     def forward(self, z, dropout_masks=None):
         _need_gpu(z, 'z'); _need_gpu(self.embed.weight, 'the module')
         masks = None
+        seq = self.whole_sequence and K.gru_dec_seq_supported(z.shape[0], self.n_hiddens, self.n_latents,
+                                                              self.n_characters, max_length)
         if self.training:
             if dropout_masks is None:
-                masks = self._device_masks(z.shape[0])
+                masks = self._device_mask_tensor(z.shape[0]) if seq else self._device_masks(z.shape[0])
             else:
                 masks = [m.to(z.device).float().contiguous() for m in dropout_masks]
                 if len(masks) != max_length or any(m.shape != (z.shape[0], self.n_hiddens) for m in masks):
                     raise ValueError('dropout_masks: %d tensors of [batch, %d]' % (max_length, self.n_hiddens))
         holder = {}
+        params = (self.embed.weight, self.z2h.weight, self.z2h.bias, self.h2o.weight, self.h2o.bias) + \
+            _cell_params(self.gru, 0) + _cell_params(self.gru, 1)
+        if seq:
+            if isinstance(masks, list):
+                masks = torch.stack(masks)
+            want_tape = torch.is_grad_enabled() and (z.requires_grad or any(p.requires_grad for p in params))
+            words = _TextDecoderSeqFn.apply(z.float(), masks, holder, want_tape, *params)
+            self.last_fed = holder.get('fed')
+            return words
         words = _TextDecoderFn.apply(z.float(), masks, holder, self.embed.weight, self.z2h.weight, self.z2h.bias,
                                      self.h2o.weight, self.h2o.bias, *(_cell_params(self.gru, 0) + _cell_params(self.gru, 1)))
         self.last_fed = holder.get('fed')
