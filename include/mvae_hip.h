@@ -565,6 +565,14 @@ typedef struct {
 } mvae_elbo_part;
 int mvae_elbo_reduce(const mvae_elbo_part *parts, int n_parts, float *elbo, int T, float *zero, size_t zero_n,
                      uint64_t *counter_dev, uint64_t counter_inc, mvae_stream_t stream);
+/* mvae_elbo_reduce whose launch also does what mvae_adam_prepare does: *step_dev += delta, then coef2[0..1] = the two
+ * bias-correction factors at the new counter value (the same double-precision expressions).  For a fused step in
+ * which nothing reads coef2 before the update at the end of the chain: the bookkeeping launch is ordered before that
+ * update anyway, so the optimizer's counter launch leaves the encoder branch it used to end. */
+int mvae_elbo_reduce_prepare(const mvae_elbo_part *parts, int n_parts, float *elbo, int T, float *zero,
+                             size_t zero_n, uint64_t *counter_dev, uint64_t counter_inc, int64_t *step_dev,
+                             int64_t delta, double lr, double beta1, double beta2, float *coef2,
+                             mvae_stream_t stream);
 /* out[g] (+)= coef[g] * sum_{r in group g} rows[r] for g < G; *total_out (+)= sum_g of those
  * (either destination may be NULL) */
 int mvae_group_sums(const float *rows, const float *coef_dev, float *out, float *total_out,

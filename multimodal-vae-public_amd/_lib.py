@@ -165,6 +165,8 @@ _SIGNATURES = {
     'mvae_linear_wgrad_batched_adam': (c_int, [ctypes.POINTER(WgradItem), c_int, ctypes.POINTER(AdamFuse), P]),
     'mvae_adam_prepare': (c_int, [P, ctypes.c_int64, c_double, c_double, c_double, P, P]),
     'mvae_elbo_reduce': (c_int, [ctypes.POINTER(ElboPart), c_int, P, c_int, P, c_size_t, P, c_uint64, P]),
+    'mvae_elbo_reduce_prepare': (c_int, [ctypes.POINTER(ElboPart), c_int, P, c_int, P, c_size_t, P, c_uint64, P,
+                                         ctypes.c_int64, c_double, c_double, c_double, P, P]),
     'mvae_philox_fill': (c_int, [P, c_size_t, c_int, c_float, c_uint64, P, c_uint64, P]),
     'mvae_randn': (c_int, [P, c_size_t, c_uint64, P, P]),
     'mvae_bernoulli': (c_int, [P, c_size_t, c_float, c_uint64, P, P]),

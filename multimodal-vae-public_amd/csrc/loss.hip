@@ -165,8 +165,8 @@ __global__ __launch_bounds__(1024) void group_sums_kernel(const float *rows, con
 struct ElboParts { mvae_elbo_part p[MVAE_ELBO_MAX_PARTS]; int n; };
 constexpr int ELBO_MAX_GROUPS = 1024;      // all parts' groups together: one thread of block 0 each
 
-__global__ __launch_bounds__(1024) void elbo_reduce_kernel(ElboParts parts, float *elbo, int T, float *zero, size_t zero_n,
-                                                           uint64_t *counter, uint64_t counter_inc) {
+__device__ __forceinline__ void elbo_reduce_body(const ElboParts &parts, float *elbo, int T, float *zero, size_t zero_n,
+                                                 uint64_t *counter, uint64_t counter_inc) {
     const size_t zstride = (size_t)gridDim.x * 1024;
     if (zero) {
         const size_t z4 = aligned16_dev(zero) ? zero_n / 4 : 0;
@@ -292,6 +292,29 @@ __global__ __launch_bounds__(1024) void elbo_reduce_kernel(ElboParts parts, floa
     }
 }
 
+__global__ __launch_bounds__(1024) void elbo_reduce_kernel(ElboParts parts, float *elbo, int T, float *zero, size_t zero_n,
+                                                           uint64_t *counter, uint64_t counter_inc) {
+    elbo_reduce_body(parts, elbo, T, zero, zero_n, counter, counter_inc);
+}
+
+// The same launch also carrying the optimizer's counter launch (mvae_adam_prepare): *step += delta and the two
+// bias-correction factors of the new step.  The LAST thread of block 0 does it, before the row sums.  In a bimodal step
+// (7 groups: waves 0..6 sum, wave 15 has no group) the two double-precision pows then run beside the other waves' memory
+// round trips; with 16 or more groups or a spread (LONG_GROUP) part wave 15 has sums of its own and does them afterwards.
+// The block's first barrier waits for this thread either way.  The placement is not timed on its own: the launch reads
+// 8.6 us in the MNIST step against 7.9 us for elbo_reduce_kernel (profiles/elbo_prepare_*_step_timeline.txt), off the chain.
+struct ElboAdam { int64_t *step; int64_t delta; double lr, b1, b2; float *coef; };
+
+__global__ __launch_bounds__(1024) void elbo_reduce_prepare_kernel(ElboParts parts, float *elbo, int T, float *zero,
+                                                                   size_t zero_n, uint64_t *counter,
+                                                                   uint64_t counter_inc, ElboAdam ad) {
+    if (blockIdx.x == 0 && threadIdx.x == 1023) {
+        *ad.step += ad.delta;
+        adam_bias_corrections(ad.lr, ad.b1, ad.b2, (double)*ad.step, ad.coef, ad.coef + 1);
+    }
+    elbo_reduce_body(parts, elbo, T, zero, zero_n, counter, counter_inc);
+}
+
 int bce_launch(BceArgs a, hipStream_t st) {
     if (!a.logits || !a.target || a.R <= 0 || a.P <= 0 || a.rows_per_group <= 0 || a.target_rows <= 0 ||
         a.target_div <= 0 || a.t_cs <= 0 || a.t_rs <= 0)
@@ -348,26 +371,51 @@ MVAE_EXPORT int mvae_ce_bwd(const float *logits, const int64_t *label, const flo
     return mvae_launch_status();
 }
 
-MVAE_EXPORT int mvae_elbo_reduce(const mvae_elbo_part *parts, int n_parts, float *elbo, int T, float *zero,
-                                 size_t zero_n, uint64_t *counter_dev, uint64_t counter_inc, mvae_stream_t stream) {
+namespace {
+// argument checks + grid of the ELBO bookkeeping launch; `ps` receives the parts by value
+int elbo_reduce_setup(const mvae_elbo_part *parts, int n_parts, const float *elbo, int T, const float *zero,
+                      size_t zero_n, ElboParts *ps, unsigned *blocks_out) {
     if (!parts || n_parts <= 0 || n_parts > MVAE_ELBO_MAX_PARTS || !elbo || T <= 0 || T > MVAE_ELBO_MAX_TERMS)
         return MVAE_ERR_ARG;
-    ElboParts ps;
-    ps.n = n_parts;
+    ps->n = n_parts;
     long total_groups = 0;
     for (int q = 0; q < n_parts; ++q) {
-        ps.p[q] = parts[q];
-        if (!ps.p[q].rows || ps.p[q].groups <= 0 || ps.p[q].rows_per_group <= 0) return MVAE_ERR_ARG;
-        if (!ps.p[q].term_of && (ps.p[q].first_term < 0 || ps.p[q].first_term + ps.p[q].groups > T)) return MVAE_ERR_ARG;
-        if (ps.p[q].rows_per_group > 1 && ps.p[q].groups > MVAE_ELBO_MAX_TERMS) return MVAE_ERR_ARG;
-        total_groups += ps.p[q].groups;
+        ps->p[q] = parts[q];
+        if (!ps->p[q].rows || ps->p[q].groups <= 0 || ps->p[q].rows_per_group <= 0) return MVAE_ERR_ARG;
+        if (!ps->p[q].term_of && (ps->p[q].first_term < 0 || ps->p[q].first_term + ps->p[q].groups > T)) return MVAE_ERR_ARG;
+        if (ps->p[q].rows_per_group > 1 && ps->p[q].groups > MVAE_ELBO_MAX_TERMS) return MVAE_ERR_ARG;
+        total_groups += ps->p[q].groups;
     }
     if (total_groups > ELBO_MAX_GROUPS) return MVAE_ERR_ARG;
     size_t blocks = zero ? (zero_n / 4 + 1023) / 1024 : 1;
     if (blocks < 1) blocks = 1;
     if (blocks > 256) blocks = 256;
-    hipLaunchKernelGGL(elbo_reduce_kernel, dim3((unsigned)blocks), dim3(1024), 0, (hipStream_t)stream, ps, elbo, T, zero,
+    *blocks_out = (unsigned)blocks;
+    return MVAE_OK;
+}
+}  // namespace
+
+MVAE_EXPORT int mvae_elbo_reduce(const mvae_elbo_part *parts, int n_parts, float *elbo, int T, float *zero,
+                                 size_t zero_n, uint64_t *counter_dev, uint64_t counter_inc, mvae_stream_t stream) {
+    ElboParts ps;
+    unsigned blocks;
+    if (int rc = elbo_reduce_setup(parts, n_parts, elbo, T, zero, zero_n, &ps, &blocks)) return rc;
+    hipLaunchKernelGGL(elbo_reduce_kernel, dim3(blocks), dim3(1024), 0, (hipStream_t)stream, ps, elbo, T, zero,
                        zero ? zero_n : 0, counter_dev, counter_inc);
+    return mvae_launch_status();
+}
+
+MVAE_EXPORT int mvae_elbo_reduce_prepare(const mvae_elbo_part *parts, int n_parts, float *elbo, int T, float *zero,
+                                         size_t zero_n, uint64_t *counter_dev, uint64_t counter_inc,
+                                         int64_t *step_dev, int64_t delta, double lr, double beta1, double beta2,
+                                         float *coef2, mvae_stream_t stream) {
+    if (!step_dev || !coef2) return MVAE_ERR_ARG;
+    ElboParts ps;
+    unsigned blocks;
+    if (int rc = elbo_reduce_setup(parts, n_parts, elbo, T, zero, zero_n, &ps, &blocks)) return rc;
+    ElboAdam ad = {step_dev, delta, lr, beta1, beta2, coef2};
+    hipLaunchKernelGGL(elbo_reduce_prepare_kernel, dim3(blocks), dim3(1024), 0, (hipStream_t)stream, ps, elbo, T, zero,
+                       zero ? zero_n : 0, counter_dev, counter_inc, ad);
     return mvae_launch_status();
 }
 

@@ -425,6 +425,10 @@ class _StepBase(object):
         if self._fusion is not None:
             self._fusion.begin()
             self._adam_prepare = lambda: optimizer.prepare_counted(self._fusion)
+        # the counter launch rides in the ELBO bookkeeping launch (mvae_elbo_reduce_prepare) when nothing reads the
+        # bias corrections before the update at the end of the chain -- not under fuse_adam, whose batches read them early
+        self._elbo_prepare = (optimizer if early and self._fusion is None and getattr(self, 'elbo_prepare', False)
+                              and hasattr(optimizer, 'prepared') else None)
         # MVAE_SPLIT_ADAM=1: the decoders' parameters (the front of the arena) are updated on the MAIN stream as soon as
         # their weight-gradient batches -- on the side stream -- are final, beside the encoders' backward; only the encoders'
         # range is left for the end of the chain (see BimodalStep._phase_b)
@@ -438,6 +442,8 @@ class _StepBase(object):
         try:
             self._body_a()
             self._phase_b('all')
+            if self._elbo_prepare is not None:
+                raise RuntimeError('the step issued no ELBO bookkeeping launch: the optimizer counter was not advanced')
             if self._adam_split is not None and self._carry.get('adam_dec_done'):
                 optimizer.step_counted_range(self._adam_split[1], self._adam_split[2], last=True)
             elif early:
@@ -449,6 +455,7 @@ class _StepBase(object):
             self._adam_counter = None
             self._fusion = None
             self._adam_split = None
+            self._elbo_prepare = None
 
     def _dp_step(self, optimizer):
         """One data-parallel step as a plain launch sequence (capturable when the communicator is): bucket k's
@@ -510,12 +517,26 @@ class _StepBase(object):
     def _early_counter(self):
         """Called at the end of the side stream's encoder forward (the shorter of the two encoder branches)."""
         if getattr(self, '_adam_counter', None) is not None:
+            if getattr(self, '_elbo_prepare', None) is not None:
+                return                      # rides in the ELBO bookkeeping launch (_elbo_reduce)
             if self._fusion is not None:
                 self._adam_prepare()        # counter + the bias corrections the fused weight-gradient launches read
             elif hasattr(self._optimizer_early, 'prepare_plain'):
                 self._optimizer_early.prepare_plain()   # counter + the step's bias corrections for the update at the end
             else:
                 K.counter_add(self._adam_counter, 1)
+
+    def _elbo_reduce(self, parts, T, zero=None, counter_inc=0):
+        """The step's ELBO bookkeeping launch -- which also advances the optimizer's step counter and leaves the step's
+        bias corrections when the captured step handed that to it (_single_gpu_step)."""
+        opt = getattr(self, '_elbo_prepare', None)
+        if opt is not None:
+            self._elbo_prepare = None
+            K.elbo_reduce_prepare(parts, self.elbo, T, *opt.prepare_plain_args(), zero=zero, counter_dev=self.counter,
+                                  counter_inc=counter_inc)
+            opt.prepared()                  # only behind a launch that was issued: step_counted() reads its factors
+        else:
+            K.elbo_reduce(parts, self.elbo, T, zero=zero, counter_dev=self.counter, counter_inc=counter_inc)
 
     def _body_a(self):
         self.model.zero_grad(set_to_none=True)
@@ -619,6 +640,9 @@ class BimodalStep(_StepBase):
         # MVAE_COUNTER_RIDES=decoder: the step-counter launch on the label DECODER's branch instead of behind the label
         # encoder's forward -- same A/B: 0.2988 vs 0.2980 ms, nothing.
         self.counter_rides = os.environ.get('MVAE_COUNTER_RIDES', 'encoder')
+        # MVAE_ELBO_PREPARE=0: the optimizer's counter launch (mvae_adam_prepare) stays a launch of its own at the end of
+        # the label encoder's forward branch instead of riding in the ELBO bookkeeping launch (A/B on one build)
+        self.elbo_prepare = os.environ.get('MVAE_ELBO_PREPARE', '1') != '0'
         self.fuse_adam = (os.environ.get('MVAE_FUSE_ADAM', '0') == '1' and self.split_dz and not self.pair_dec)
         # per-term loss coefficients lambda/B, beta/B: pinned host mirror -> device, so a captured
         # graph sees new annealing factors without re-capture
@@ -1077,7 +1101,7 @@ class BimodalStep(_StepBase):
             c['elbo_late'] = (elbo_parts, counter_inc)
         else:
             dz = torch.empty(T, B, D, dtype=torch.float32, device=self.dev)
-            K.elbo_reduce(elbo_parts, self.elbo, T, zero=dz, counter_dev=self.counter, counter_inc=counter_inc)
+            self._elbo_reduce(elbo_parts, T, zero=dz, counter_inc=counter_inc)
             # ---- both decoders' first layers -> the shared dz
             L.first_linear_dgrad(m.image_decoder.plan(), g_img, dz[i0:i0 + ni].reshape(ni * B, D), True)
             L.first_linear_dgrad(m.label_decoder.plan(), g_lbl, dz[l0:l0 + nl].reshape(nl * B, D), True)
@@ -1091,7 +1115,7 @@ class BimodalStep(_StepBase):
         """The step's ELBO sums + Philox counter advance (split-dz mode): off the decoder -> PoE -> encoder chain."""
         late = self._carry.pop('elbo_late', None)
         if late is not None:
-            K.elbo_reduce(late[0], self.elbo, self.T, counter_dev=self.counter, counter_inc=late[1])
+            self._elbo_reduce(late[0], self.T, counter_inc=late[1])
 
     def _phase_b(self, part='all'):
         """PoE backward + encoders backward.  ``part``: 'all', or for a data-parallel replica with three

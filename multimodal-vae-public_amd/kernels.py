@@ -871,9 +871,7 @@ def group_sums(rows, coef, out, total, G, rows_per_group, accumulate=False):
                                      ACCUMULATE if accumulate else 0, _stream()), 'mvae_group_sums')
 
 
-def elbo_reduce(parts, elbo, T, zero=None, counter_dev=None, counter_inc=0):
-    """parts: [(rows, coef or None, term_of or None, first_term, groups, rows_per_group)] -- see
-    mvae_elbo_reduce in include/mvae_hip.h.  Overwrites elbo[0..T]."""
+def _elbo_parts(parts):
     if not 0 < len(parts) <= _lib.ELBO_MAX_PARTS:
         raise RuntimeError('1..%d ELBO parts per launch' % _lib.ELBO_MAX_PARTS)
     arr = (_lib.ElboPart * len(parts))()
@@ -882,10 +880,29 @@ def elbo_reduce(parts, elbo, T, zero=None, counter_dev=None, counter_inc=0):
         if rows.numel() < groups * rpg:
             raise RuntimeError('ELBO part %d: %d values for %d x %d' % (q, rows.numel(), groups, rpg))
         arr[q] = _lib.ElboPart(_ptr(rows), _ptr(coef), _ptr(term_of), int(first), int(groups), int(rpg))
+    return arr
+
+
+def elbo_reduce(parts, elbo, T, zero=None, counter_dev=None, counter_inc=0):
+    """parts: [(rows, coef or None, term_of or None, first_term, groups, rows_per_group)] -- see
+    mvae_elbo_reduce in include/mvae_hip.h.  Overwrites elbo[0..T]."""
+    arr = _elbo_parts(parts)
     _need_gpu(elbo, zero, counter_dev); _f32c(elbo, zero)
     check(_lib.lib().mvae_elbo_reduce(arr, len(parts), _ptr(elbo), int(T), _ptr(zero),
                                       0 if zero is None else zero.numel(), _ptr(counter_dev), int(counter_inc),
                                       _stream()), 'mvae_elbo_reduce')
+
+
+def elbo_reduce_prepare(parts, elbo, T, step_dev, delta, lr, beta1, beta2, coef2, zero=None, counter_dev=None,
+                        counter_inc=0):
+    """``elbo_reduce`` and ``adam_prepare(step_dev, delta, lr, beta1, beta2, coef2)`` in one launch
+    (mvae_elbo_reduce_prepare)."""
+    arr = _elbo_parts(parts)
+    _need_gpu(elbo, zero, counter_dev, step_dev, coef2); _f32c(elbo, zero, coef2)
+    check(_lib.lib().mvae_elbo_reduce_prepare(arr, len(parts), _ptr(elbo), int(T), _ptr(zero),
+                                              0 if zero is None else zero.numel(), _ptr(counter_dev),
+                                              int(counter_inc), _ptr(step_dev), int(delta), lr, beta1, beta2,
+                                              _ptr(coef2), _stream()), 'mvae_elbo_reduce_prepare')
 
 
 # ---------------------------------------------------------------------------- noise / optimiser

@@ -159,6 +159,16 @@ class FusedAdam(torch.optim.Optimizer):
         K.adam_prepare(self.step_counter(), 1, g['lr'], g['betas'][0], g['betas'][1], self._coef)
         self._coef_ready = True
 
+    def prepare_plain_args(self):
+        """The arguments ``prepare_plain()`` gives ``K.adam_prepare``, for a caller that folds the counter launch into a
+        launch of its own (mvae_elbo_reduce_prepare) and calls ``prepared()`` once that launch is issued."""
+        g = self.param_groups[0]
+        return self.step_counter(), 1, g['lr'], g['betas'][0], g['betas'][1], self._coef
+
+    def prepared(self):
+        """The caller's own launch did what ``prepare_plain()`` does; it must be ordered before ``step_counted()``."""
+        self._coef_ready = True
+
     def _apply_counted(self, lo, hi):
         arena, g = self._arena, self.param_groups[0]
         if self._coef_ready:
