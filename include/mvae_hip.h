@@ -750,6 +750,41 @@ int mvae_gru_dec_seq_bwd(const float *dwords, const float *w_ih0, const float *w
                          mvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * K19  The whole TextEncoder in one launch per direction (csrc/gru_enc_seq.hip): the embedding gathers, the L cells of
+ *      the forward-direction GRU, the ONE cell of the reverse direction that x[-1] uses (on position L-1, from h = 0),
+ *      s = h_L + h_b and out = s . W_h2p^T + b_h2p.  Ownership as K18: a workgroup owns 16 batch rows for the whole
+ *      sequence; workgroups never communicate (no grid barrier, flag or atomic).  All buffers are contiguous fp32
+ *      (x, idx_all: int64), weights in nn.GRU / nn.Linear layout: w_ih, w_hh (and the reverse pair) [3H, H],
+ *      w_h2p [P, H] with P = 2 * n_latents, w_emb [n_chars, H].
+ *   gru_enc_seq_supported  host-only: 1 where both kernels' LDS plans fit the CU's 160 KiB, H, P, L <= 4096,
+ *                 B * 4H < 2^31 and bidirectional is 0 or 1; else 0 (any size <= 0 included).  No alignment needed.
+ *   gru_enc_seq_fwd  x [B, L] -> out [B, P].  Characters are clamped to [0, n_chars) before any address is formed.
+ *                 Unidirectional: the four reverse parameters are null (all four or none).  The tape (all five of
+ *                 e_all, h_all, gates, s, idx_all, plus gates_r exactly when bidirectional; or none of them) is
+ *                 time-major: e_all [L, B, H]; h_all [L+1, B, H] (slot 0 zeros, slot t+1 the state after position t);
+ *                 gates [L, B, 4H] and gates_r [B, 4H] (r | z | n | gh_n); s [B, H]; idx_all [L, B] the clamped
+ *                 characters.  Without a tape nothing but out is written.
+ *   gru_enc_seq_bwd  dout [B, P] and the tape -> dgi_all, dgh_all [L, B, 3H], de_all [L, B, H] (gradient of the
+ *                 gathered embeddings; position L-1 includes the reverse cell's part) and, bidirectional (w_ih_r,
+ *                 gates_r, dgi_r, dgh_r: all four or none), dgi_r, dgh_r [B, 3H].  No weight gradients: those are
+ *                 Linear weight-gradient launches on the [L * B, .] views and one embedding backward on idx_all.
+ *   Both return MVAE_ERR_ARG before any launch on a null required pointer, a partial tape or reverse set, gates_r
+ *   without reverse parameters, or an unsupported geometry.
+ * ------------------------------------------------------------------------------------ */
+int mvae_gru_enc_seq_supported(int B, int H, int P, int n_chars, int L, int bidirectional);
+int mvae_gru_enc_seq_fwd(const int64_t *x, const float *w_emb, const float *w_ih, const float *w_hh, const float *b_ih,
+                         const float *b_hh, const float *w_ih_r /* nullable */, const float *w_hh_r /* nullable */,
+                         const float *b_ih_r /* nullable */, const float *b_hh_r /* nullable */, const float *w_h2p,
+                         const float *b_h2p, float *out, float *e_all, float *h_all, float *gates,
+                         float *gates_r /* nullable */, float *s, int64_t *idx_all, int B, int H, int P, int n_chars,
+                         int L, mvae_stream_t stream);
+int mvae_gru_enc_seq_bwd(const float *dout, const float *w_h2p, const float *w_ih, const float *w_hh,
+                         const float *w_ih_r /* nullable */, const float *h_all, const float *gates,
+                         const float *gates_r /* nullable */, float *dgi_all, float *dgh_all,
+                         float *dgi_r /* nullable */, float *dgh_r /* nullable */, float *de_all, int B, int H, int P,
+                         int n_chars, int L, mvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * C1  Gradient exchange of data-parallel replicas -- RCCL over xGMI.
  *     The reference has NO counterpart: it is single-process, single-device (no DataParallel, no
  *     torch.distributed anywhere; README.md:47 `CUDA_VISIBLE_DEVICES=0`).  What this replaces is what N

@@ -199,6 +199,10 @@ _SIGNATURES = {
     'mvae_gru_dec_seq_supported': (c_int, [c_int] * 5),
     'mvae_gru_dec_seq_fwd': (c_int, [P] * 14 + [c_float] + [P] * 9 + [c_int] * 6 + [P]),
     'mvae_gru_dec_seq_bwd': (c_int, [P] * 7 + [c_float] + [P] * 12 + [c_int] * 5 + [P]),
+    # K19: the whole TextEncoder in one launch per direction
+    'mvae_gru_enc_seq_supported': (c_int, [c_int] * 6),
+    'mvae_gru_enc_seq_fwd': (c_int, [P] * 19 + [c_int] * 5 + [P]),
+    'mvae_gru_enc_seq_bwd': (c_int, [P] * 13 + [c_int] * 5 + [P]),
     # C1: the gradient exchange (RCCL bound at run time)
     'mvae_comm_use_library': (c_int, [ctypes.c_char_p]),
     'mvae_comm_rccl_version': (c_int, []),

@@ -1170,3 +1170,67 @@ def gru_dec_seq_bwd(dwords, p0, p1, w_h2o, masks, mask_scale, h0_all, h1_all, ga
                                           _ptr(gates1), _ptr(dgi0_all), _ptr(dgh0_all), _ptr(dgi1_all), _ptr(dgh1_all),
                                           _ptr(demb_all), _ptr(dlog_all), _ptr(dhz), _ptr(dz), B, H, D, n_chars, L,
                                           _stream()), 'mvae_gru_dec_seq_bwd')
+
+
+# ---------------------------------------------------------------------------- whole-sequence TextEncoder (MultiMNIST)
+def gru_enc_seq_supported(B, H, P, n_chars, L, bidirectional):
+    """Whether the one-launch encoder kernels take this geometry (host-only query, no GPU needed).  ``P`` is the width
+    of ``h2p``'s output, 2 * n_latents."""
+    return bool(_lib.lib().mvae_gru_enc_seq_supported(int(B), int(H), int(P), int(n_chars), int(L),
+                                                      1 if bidirectional else 0))
+
+
+def _enc_cell_weights(p, H, sfx, with_bias=True):
+    _shaped(p[0], (3 * H, H), 'weight_ih_l0' + sfx); _shaped(p[1], (3 * H, H), 'weight_hh_l0' + sfx)
+    if with_bias:
+        _shaped(p[2], (3 * H,), 'bias_ih_l0' + sfx); _shaped(p[3], (3 * H,), 'bias_hh_l0' + sfx)
+
+
+def gru_enc_seq_fwd(x, w_emb, pf, pr, w_h2p, b_h2p, out, tape):
+    """The whole TextEncoder in one launch: ``x`` [B, L] int64 -> ``out`` [B, P].  ``pf`` / ``pr`` = (w_ih, w_hh, b_ih,
+    b_hh) of the forward / reverse direction (``pr`` None: unidirectional); ``tape`` = (e_all, h_all, gates, gates_r,
+    s, idx_all) with ``gates_r`` None exactly when ``pr`` is, or None: nothing but ``out`` is written."""
+    B, L = x.shape
+    n_chars, H = w_emb.shape
+    P = w_h2p.shape[0]
+    _shaped(x, (B, L), 'text', torch.int64); _shaped(w_emb, (n_chars, H), 'embed.weight')
+    _enc_cell_weights(pf, H, '')
+    if pr is not None:
+        _enc_cell_weights(pr, H, '_reverse')
+    _shaped(w_h2p, (P, H), 'h2p.weight'); _shaped(b_h2p, (P,), 'h2p.bias'); _shaped(out, (B, P), 'out')
+    tp = [None] * 6
+    if tape is not None:
+        e_all, h_all, gates, gates_r, s, idx_all = tape
+        _shaped(e_all, (L, B, H), 'e_all'); _shaped(h_all, (L + 1, B, H), 'h_all'); _shaped(gates, (L, B, 4 * H), 'gates')
+        if (gates_r is None) != (pr is None):
+            raise RuntimeError('gates_r goes with the reverse direction: both or neither')
+        if gates_r is not None:
+            _shaped(gates_r, (B, 4 * H), 'gates_r')
+        _shaped(s, (B, H), 's'); _shaped(idx_all, (L, B), 'idx_all', torch.int64)
+        tp = [_ptr(t) for t in tape]
+    rp = [_ptr(t) for t in pr] if pr is not None else [None] * 4
+    check(_lib.lib().mvae_gru_enc_seq_fwd(_ptr(x), _ptr(w_emb), _ptr(pf[0]), _ptr(pf[1]), _ptr(pf[2]), _ptr(pf[3]), *rp,
+                                          _ptr(w_h2p), _ptr(b_h2p), _ptr(out), *tp, B, H, P, n_chars, L, _stream()),
+          'mvae_gru_enc_seq_fwd')
+
+
+def gru_enc_seq_bwd(dout, w_h2p, pf, pr, n_chars, h_all, gates, gates_r, dgi_all, dgh_all, dgi_r, dgh_r, de_all):
+    """The reverse recurrence of ``gru_enc_seq_fwd`` in one launch: the time-stacked pre-activation gradients of the
+    forward direction, those of the reverse direction's one cell (``pr``, ``gates_r``, ``dgi_r``, ``dgh_r``: all or
+    none) and the gradient of the gathered embeddings.  No weight gradients."""
+    B, P = dout.shape
+    L, _, H = de_all.shape
+    _shaped(dout, (B, P), 'dout'); _shaped(w_h2p, (P, H), 'h2p.weight')
+    _enc_cell_weights(pf, H, '', with_bias=False)
+    _shaped(h_all, (L + 1, B, H), 'h_all'); _shaped(gates, (L, B, 4 * H), 'gates')
+    _shaped(dgi_all, (L, B, 3 * H), 'dgi_all'); _shaped(dgh_all, (L, B, 3 * H), 'dgh_all'); _shaped(de_all, (L, B, H), 'de_all')
+    rev = (pr, gates_r, dgi_r, dgh_r)
+    if any(t is None for t in rev) and not all(t is None for t in rev):
+        raise RuntimeError('the reverse direction (parameters, gates_r, dgi_r, dgh_r): all or none')
+    if pr is not None:
+        _enc_cell_weights(pr, H, '_reverse', with_bias=False)
+        _shaped(gates_r, (B, 4 * H), 'gates_r'); _shaped(dgi_r, (B, 3 * H), 'dgi_r'); _shaped(dgh_r, (B, 3 * H), 'dgh_r')
+    check(_lib.lib().mvae_gru_enc_seq_bwd(_ptr(dout), _ptr(w_h2p), _ptr(pf[0]), _ptr(pf[1]),
+                                          _ptr(pr[0]) if pr is not None else None, _ptr(h_all), _ptr(gates),
+                                          _ptr(gates_r), _ptr(dgi_all), _ptr(dgh_all), _ptr(dgi_r), _ptr(dgh_r),
+                                          _ptr(de_all), B, H, P, int(n_chars), L, _stream()), 'mvae_gru_enc_seq_bwd')

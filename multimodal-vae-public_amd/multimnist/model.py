@@ -24,7 +24,8 @@ forward and backward are hand-written (``torch.autograd.Function`` shells), no A
 evaluates but never uses is not evaluated: the backward direction of the encoder's GRU contributes only its FIRST
 step (on the last character) to ``x[-1]`` (:177).  The latent path (PoE, draw, KL) is the fused ``mvae_poe_*`` launch of
 the other four models.  The decoder's four greedy steps run as one launch per direction (csrc/gru_seq.hip) where
-``TextDecoder.whole_sequence`` is set; the per-cell launches remain as the fallback.  There is no fused or captured
+``TextDecoder.whole_sequence`` is set, the encoder as one launch per direction (csrc/gru_enc_seq.hip) where
+``TextEncoder.whole_sequence`` is; the per-cell launches remain as the fallback.  There is no fused or captured
 MultiMNIST step: ``train.py`` runs the modules eagerly."""
 import warnings
 
@@ -157,8 +158,65 @@ class _TextEncoderFn(torch.autograd.Function):
         return (None, None, dw_emb, dw_h2p, db_h2p) + gf + grads_r
 
 
+class _TextEncoderSeqFn(torch.autograd.Function):
+    """The encoder on the whole-sequence kernels (csrc/gru_enc_seq.hip): ONE launch for the gathers, the L + 1 cells, the
+    direction sum and h2p; backward: ONE launch for the reverse recurrence, then the weight gradients as Linear launches
+    on the time-stacked [L * B, .] tapes and one embedding backward -- seven launches, five when unidirectional.
+    ``want_tape`` is False under ``no_grad``: nothing but the output is stored then."""
+    @staticmethod
+    def forward(ctx, x, bidirectional, want_tape, w_emb, w_h2p, b_h2p, *gru_params):
+        B, L = x.shape
+        H = w_emb.shape[1]
+        pf = gru_params[:4]
+        pr = gru_params[4:8] if bidirectional else None
+        out = _new(B, w_h2p.shape[0], like=w_emb)
+        tape = None
+        if want_tape:
+            tape = (_new(L, B, H, like=w_emb), _new(L + 1, B, H, like=w_emb), _new(L, B, 4 * H, like=w_emb),
+                    _new(B, 4 * H, like=w_emb) if bidirectional else None, _new(B, H, like=w_emb),
+                    torch.empty(L, B, dtype=torch.int64, device=w_emb.device))
+        K.gru_enc_seq_fwd(x, w_emb, pf, pr, w_h2p, b_h2p, out, tape)
+        ctx.tapes = tape
+        ctx.params = (w_emb, w_h2p, pf, pr)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        tape = ctx.tapes
+        if tape is None:
+            raise RuntimeError('TextEncoder: backward through a forward that ran without gradient tracking')
+        e_all, h_all, gates, gates_r, s, idx_all = tape
+        w_emb, w_h2p, pf, pr = ctx.params
+        L, B, H = e_all.shape
+        dout = dout.contiguous()
+        dgi, dgh, de = _new(L, B, 3 * H, like=w_emb), _new(L, B, 3 * H, like=w_emb), _new(L, B, H, like=w_emb)
+        dgi_r = dgh_r = None
+        if pr is not None:
+            dgi_r, dgh_r = _new(B, 3 * H, like=w_emb), _new(B, 3 * H, like=w_emb)
+        K.gru_enc_seq_bwd(dout, w_h2p, pf, pr, w_emb.shape[0], h_all, gates, gates_r, dgi, dgh, dgi_r, dgh_r, de)
+        dw_h2p, db_h2p = torch.empty_like(w_h2p), _new(w_h2p.shape[0], like=w_emb)
+        K.linear_wgrad(dout, s, dw_h2p, db_h2p)
+        R = L * B
+        gf = tuple(torch.empty_like(p) for p in pf)
+        K.linear_wgrad(dgi.view(R, 3 * H), e_all.view(R, H), gf[0], gf[2])
+        K.linear_wgrad(dgh.view(R, 3 * H), h_all[:L].view(R, H), gf[1], gf[3])        # h_prev of position t = slot t
+        grads_r = ()
+        if pr is not None:
+            grads_r = tuple(torch.empty_like(p) for p in pr)
+            K.linear_wgrad(dgi_r, e_all[L - 1], grads_r[0], grads_r[2])
+            K.linear_wgrad(dgh_r, h_all[0], grads_r[1], grads_r[3])                   # h_prev = 0: weight_hh's is zero
+        dw_emb = torch.empty_like(w_emb)
+        K.embedding_bwd(idx_all.view(R), w_emb, de.view(R, H), dw_emb)
+        ctx.tapes = None
+        return (None, None, None, dw_emb, dw_h2p, db_h2p) + gf + grads_r
+
+
 class TextEncoder(nn.Module):
-    """Parametrizes q(z|y) (multimnist/model.py:145-179)."""
+    """Parametrizes q(z|y) (multimnist/model.py:145-179).  ``whole_sequence`` (an attribute, not a constructor argument)
+    selects the one-launch kernels of csrc/gru_enc_seq.hip where ``kernels.gru_enc_seq_supported`` takes the geometry;
+    False runs the per-cell launches."""
+    WHOLE_SEQUENCE_DEFAULT = True       # profiles/multimnist_gru_enc_seq.txt
+
     def __init__(self, n_latents, n_characters, n_hiddens=200, bidirectional=True):
         super().__init__()
         self.embed = nn.Embedding(n_characters, n_hiddens)
@@ -169,6 +227,7 @@ class TextEncoder(nn.Module):
         self.n_latents = n_latents
         self.n_hiddens = n_hiddens
         self.bidirectional = bidirectional
+        self.whole_sequence = self.WHOLE_SEQUENCE_DEFAULT
 
     def heads(self, x):
         """The [batch, 2D] output of ``h2p`` (mu | logvar), as the fused PoE launch takes it."""
@@ -176,6 +235,11 @@ class TextEncoder(nn.Module):
         if x.dim() != 2 or x.dtype != torch.int64:
             raise ValueError('text must be an int64 [batch, length] tensor of character indices')
         params = _cell_params(self.gru, 0) + (_cell_params(self.gru, 0, True) if self.bidirectional else ())
+        if self.whole_sequence and K.gru_enc_seq_supported(x.shape[0], self.n_hiddens, 2 * self.n_latents,
+                                                           self.embed.weight.shape[0], x.shape[1], self.bidirectional):
+            all_params = (self.embed.weight, self.h2p.weight, self.h2p.bias) + params
+            want_tape = torch.is_grad_enabled() and any(p.requires_grad for p in all_params)
+            return _TextEncoderSeqFn.apply(x.contiguous(), self.bidirectional, want_tape, *all_params)
         return _TextEncoderFn.apply(x.contiguous(), self.bidirectional, self.embed.weight, self.h2p.weight, self.h2p.bias,
                                     *params)
 
