@@ -785,6 +785,37 @@ int mvae_gru_enc_seq_bwd(const float *dout, const float *w_h2p, const float *w_i
                          int n_chars, int L, mvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * K20  Importance-weighted marginal log-likelihood (csrc/loglike.hip): the element work of the `loglike.py` the
+ *      reference's README names in every experiment folder ("to compute the marginal log likelihood log p(x) using
+ *      q(z|x,y) as the inference network", README.md) but never published.  With K samples per
+ *      datum the decoders and the loss-row kernels (K11, K13) run on the K * B rows between these two launches.
+ *   iw_draw        mu, logvar [B, D] with row stride ld (column ranges of a heads buffer) -> z [Kc, B, D] contiguous,
+ *                  sample-major (row r = k * B + b belongs to datum r % B: the addressing mvae_ce_fwd's label_rows and
+ *                  mvae_bce_rowsum_fwd's target_rows already use, so the decoders take z as a plain batch of Kc * B rows)
+ *                  and lw [Kc, B]:   z = mu + exp(0.5 logvar) * eps,
+ *                  lw[k, b] = sum_d 0.5 eps^2 - 0.5 z^2 + 0.5 logvar  (= log p(z) - log q(z | x); the 2 pi terms cancel).
+ *                  eps [Kc, B, D] given: used as is (parity runs).  eps NULL: generated in the launch -- exactly the
+ *                  standard normals mvae_philox_fill(seed, *counter_dev + counter_offset) would write for a [Kc, B, D]
+ *                  array (the contract of mvae_poe_fwd_draw); the counter is not advanced.  eps_out (nullable) receives
+ *                  the noise used.  One wave per row, lanes along d, fixed reduction order: a row's lw does not depend
+ *                  on Kc or B.  MVAE_ERR_ARG on a non-positive size, ld < D, a null pointer, Kc * B >= 2^31.
+ *   iw_accumulate  folds a chunk of log-weights  logw[k, b] = lw[k, b] - sum_j rec_a[(k * B + b) * rows_a + j]
+ *                  - sum_j rec_b[(k * B + b) * rows_b + j]  (rec_*: nullable loss rows, i.e. -log p, in the same
+ *                  sample-major order; rows_* rows per sample: 1, or 4 for the [Kc, B, 4] text rows) into
+ *                  state [B, 2] = (running maximum, running sum of exp(logw - maximum)) by the online log-sum-exp merge.
+ *                  The caller initialises state to (-inf, 0); the maximum is subtracted before every exp and a -inf
+ *                  maximum is never subtracted from itself.  finish_k > 0 (the TOTAL number of samples folded so far,
+ *                  this chunk included) also writes out[b] = maximum + log(sum) - log(finish_k).  One wave per datum,
+ *                  lanes along k, wave maximum then wave sum: no atomics, deterministic.
+ * ------------------------------------------------------------------------------------ */
+int mvae_iw_draw(const float *mu, const float *logvar, int ld, const float *eps /* nullable */, uint64_t seed,
+                 const uint64_t *counter_dev /* nullable with eps */, uint64_t counter_offset,
+                 float *eps_out /* nullable */, float *z, float *lw, int Kc, int B, int D, mvae_stream_t stream);
+int mvae_iw_accumulate(const float *lw, const float *rec_a /* nullable */, int rows_a,
+                       const float *rec_b /* nullable */, int rows_b, float *state, float *out /* nullable */,
+                       int Kc, int B, int finish_k, mvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * C1  Gradient exchange of data-parallel replicas -- RCCL over xGMI.
  *     The reference has NO counterpart: it is single-process, single-device (no DataParallel, no
  *     torch.distributed anywhere; README.md:47 `CUDA_VISIBLE_DEVICES=0`).  What this replaces is what N

@@ -10,10 +10,14 @@ hyphen) or ``importlib.import_module('multimodal-vae-public_amd')``.
     mvae_amd.optim.FusedAdam                                          one-launch Adam over the arena
     mvae_amd.parallel.DataParallel                                    RCCL gradient all-reduce
     mvae_amd.capture_step(body, example_args, model=, optimizer=)     the reference's unchanged loop body as ONE hipGraph
+    mvae_amd.log_likelihood(model, image=, label=, score=, given=)    importance-weighted marginal log-likelihood
 """
 from . import _lib, kernels, arena, layers, functional, base, engine, optim, parallel, graph  # noqa: F401
 from .graph import capture_step  # noqa: F401
+from . import loglike  # noqa: F401
+from .loglike import log_likelihood  # noqa: F401
 from . import mnist, fashionmnist, celeba, celeba19  # noqa: F401
 
 __all__ = ['kernels', 'arena', 'layers', 'functional', 'base', 'engine', 'optim', 'parallel', 'graph', 'capture_step',
+           'loglike', 'log_likelihood',
            'mnist', 'fashionmnist', 'celeba', 'celeba19']

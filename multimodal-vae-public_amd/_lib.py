@@ -203,6 +203,9 @@ _SIGNATURES = {
     'mvae_gru_enc_seq_supported': (c_int, [c_int] * 6),
     'mvae_gru_enc_seq_fwd': (c_int, [P] * 19 + [c_int] * 5 + [P]),
     'mvae_gru_enc_seq_bwd': (c_int, [P] * 13 + [c_int] * 5 + [P]),
+    # K20: the importance-weighted log-likelihood (draw + density ratio, streaming log-mean-exp)
+    'mvae_iw_draw': (c_int, [P, P, c_int, P, c_uint64, P, c_uint64, P, P, P, c_int, c_int, c_int, P]),
+    'mvae_iw_accumulate': (c_int, [P, P, c_int, P, c_int, P, P, c_int, c_int, c_int, P]),
     # C1: the gradient exchange (RCCL bound at run time)
     'mvae_comm_use_library': (c_int, [ctypes.c_char_p]),
     'mvae_comm_rccl_version': (c_int, []),

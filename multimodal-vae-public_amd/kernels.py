@@ -1234,3 +1234,55 @@ def gru_enc_seq_bwd(dout, w_h2p, pf, pr, n_chars, h_all, gates, gates_r, dgi_all
                                           _ptr(pr[0]) if pr is not None else None, _ptr(h_all), _ptr(gates),
                                           _ptr(gates_r), _ptr(dgi_all), _ptr(dgh_all), _ptr(dgi_r), _ptr(dgh_r),
                                           _ptr(de_all), B, H, P, int(n_chars), L, _stream()), 'mvae_gru_enc_seq_bwd')
+
+
+# ---------------------------------------------------------------------------- importance-weighted log-likelihood (K20)
+def iw_draw(mu, logvar, z, lw, eps=None, seed=0, counter_dev=None, counter_offset=0, eps_out=None):
+    """``z[Kc, B, D] = mu + exp(0.5 logvar) * eps`` and the density-ratio rows ``lw[Kc, B]`` (mvae_iw_draw).  ``mu`` /
+    ``logvar`` are [B, D] with unit column stride and a common row stride (column ranges of a heads buffer qualify).
+    ``eps`` [Kc, B, D] replays a host draw; without it the launch generates what ``philox_fill(seed, counter_dev,
+    counter_offset)`` would write for a [Kc, B, D] array and (optionally) stores it to ``eps_out``."""
+    _need_gpu(mu, logvar, z, lw, eps, counter_dev, eps_out); _f32c(z, lw, eps, eps_out)
+    if z.dim() != 3 or mu.dim() != 2 or mu.shape != logvar.shape or tuple(z.shape[1:]) != tuple(mu.shape):
+        raise RuntimeError('iw_draw: mu / logvar [B, D] and z [Kc, B, D]; got %s, %s, %s'
+                           % (tuple(mu.shape), tuple(logvar.shape), tuple(z.shape)))
+    Kc, B, D = z.shape
+    for t in (mu, logvar):
+        if t.dtype != torch.float32 or (D > 1 and t.stride(1) != 1) or (B > 1 and t.stride(0) != mu.stride(0)):
+            raise RuntimeError('iw_draw: mu and logvar must be float32 with unit column stride and one row stride')
+    ld = mu.stride(0) if B > 1 else max(D, mu.stride(0))
+    if lw.numel() != Kc * B:
+        raise RuntimeError('iw_draw: lw holds %d values for %d x %d rows' % (lw.numel(), Kc, B))
+    for t, what in ((eps, 'eps'), (eps_out, 'eps_out')):
+        if t is not None and t.numel() != z.numel():
+            raise RuntimeError('iw_draw: %s holds %d values for z of %d' % (what, t.numel(), z.numel()))
+    if eps is None and (counter_dev is None or counter_dev.dtype != torch.int64):
+        raise RuntimeError('iw_draw: the device draw needs an int64 launch counter on the GPU')
+    check(_lib.lib().mvae_iw_draw(_ptr(mu), _ptr(logvar), int(ld), _ptr(eps), int(seed), _ptr(counter_dev),
+                                  int(counter_offset), _ptr(eps_out), _ptr(z), _ptr(lw), Kc, B, D, _stream()),
+          'mvae_iw_draw')
+
+
+def iw_accumulate(lw, terms, state, out=None, finish_k=0):
+    """Fold the chunk ``lw[Kc, B]`` minus its reconstruction rows into ``state[B, 2]`` (running maximum, running sum of
+    exp(. - maximum); start it at (-inf, 0)) -- mvae_iw_accumulate.  ``terms``: up to two ``(rows, rows_per_sample)``
+    pairs of loss rows (-log p) in the same sample-major order.  ``finish_k`` = the total number of samples folded so
+    far, this chunk included, also writes ``out[b] = logsumexp - log(finish_k)``."""
+    _need_gpu(lw, state, out); _f32c(lw, state, out)
+    if lw.dim() != 2 or tuple(state.shape) != (lw.shape[1], 2):
+        raise RuntimeError('iw_accumulate: lw [Kc, B] and state [B, 2]; got %s and %s' % (tuple(lw.shape), tuple(state.shape)))
+    Kc, B = lw.shape
+    terms = list(terms)
+    if len(terms) > 2:
+        raise RuntimeError('iw_accumulate: at most two reconstruction terms per launch')
+    args = []
+    for rows, rps in terms:
+        _need_gpu(rows); _f32c(rows)
+        if int(rps) < 1 or rows.numel() != Kc * B * int(rps):
+            raise RuntimeError('iw_accumulate: a term holds %d rows for %d x %d samples of %d' % (rows.numel(), Kc, B, rps))
+        args += [_ptr(rows), int(rps)]
+    args += [None, 0] * (2 - len(terms))
+    if finish_k and (out is None or out.numel() != B):
+        raise RuntimeError('iw_accumulate: finish needs out [B]')
+    check(_lib.lib().mvae_iw_accumulate(_ptr(lw), *args, _ptr(state), _ptr(out), Kc, B, int(finish_k), _stream()),
+          'mvae_iw_accumulate')
