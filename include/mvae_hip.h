@@ -816,6 +816,36 @@ int mvae_iw_accumulate(const float *lw, const float *rec_a /* nullable */, int r
                        int Kc, int B, int finish_k, mvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * K21  MultiMNIST dataset builder (csrc/multimnist_data.hip): the compose step of multimnist/datasets.py:107-146 --
+ *      0-4 MNIST digits, each resized to w x w (scipy.misc.imresize = Pillow's 8-bit BILINEAR), padded to its place
+ *      on a 50 x 50 canvas, summed; "crude check for overlapping digits": np.max(canvas) > 255 -- for M canvases in
+ *      ONE launch over a digit bank resident in HBM.
+ *   bank   uint8 [n_bank, 28, 28], 4-byte aligned.
+ *   plan   int32 [M, MVAE_MM_PLAN_STRIDE] on the device: n (0..4), then four records (bank index, w, top, left);
+ *          records past n are not read.  The digit lands on rows top..top+w, columns left..left+w (np.pad's first
+ *          pair pads rows).  The caller validates: 0 <= index < n_bank, MVAE_MM_WMIN <= w <= MVAE_MM_WMAX,
+ *          0 <= top, top + w <= 50, the same for left.  A canvas whose plan breaks one of these is not composed:
+ *          it comes out all zero with flag -1.
+ *   kk     int32 [44, 50, MVAE_MM_KSIZE], bounds int32 [44, 50, 2] on the device: for every width w, slice
+ *          w - MVAE_MM_WMIN holds the host tables of mvae_resample_coeffs(28, w) (rows of ksize(28, w) <= 9
+ *          coefficients, zero-padded to 9; rows past w unused).  One table serves both passes.
+ *   canvas uint8 [M, 50, 50], 4-byte aligned: min(sum, 255) -- exact wherever flags is 0.
+ *   flags  int32 [M]: 1 if any pixel sum exceeds 255 (a sum of exactly 255 is not flagged), else 0.
+ *   Horizontal pass first, uint8 intermediate, then the vertical pass, like mvae_resize_crop_u8_to_f32; w = 28 is
+ *   the identity.  One 256-thread block per canvas; integer sums, no atomics, deterministic.
+ *   Null pointers, M <= 0, n_bank <= 0 or a misaligned bank / canvas: MVAE_ERR_ARG before any launch.
+ * ------------------------------------------------------------------------------------ */
+#define MVAE_MM_DIGIT 28
+#define MVAE_MM_CANVAS 50
+#define MVAE_MM_MAX_DIGITS 4
+#define MVAE_MM_PLAN_STRIDE 17
+#define MVAE_MM_WMIN 7
+#define MVAE_MM_WMAX 50
+#define MVAE_MM_KSIZE 9
+int mvae_multimnist_compose(const uint8_t *bank, int n_bank, const int *plan_dev, int M, const int *kk_dev,
+                            const int *bounds_dev, uint8_t *canvas, int *flags, mvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * C1  Gradient exchange of data-parallel replicas -- RCCL over xGMI.
  *     The reference has NO counterpart: it is single-process, single-device (no DataParallel, no
  *     torch.distributed anywhere; README.md:47 `CUDA_VISIBLE_DEVICES=0`).  What this replaces is what N

@@ -206,6 +206,8 @@ _SIGNATURES = {
     # K20: the importance-weighted log-likelihood (draw + density ratio, streaming log-mean-exp)
     'mvae_iw_draw': (c_int, [P, P, c_int, P, c_uint64, P, c_uint64, P, P, P, c_int, c_int, c_int, P]),
     'mvae_iw_accumulate': (c_int, [P, P, c_int, P, c_int, P, P, c_int, c_int, c_int, P]),
+    # K21: the MultiMNIST dataset builder's compose step
+    'mvae_multimnist_compose': (c_int, [P, c_int, P, c_int, P, P, P, P, P]),
     # C1: the gradient exchange (RCCL bound at run time)
     'mvae_comm_use_library': (c_int, [ctypes.c_char_p]),
     'mvae_comm_rccl_version': (c_int, []),

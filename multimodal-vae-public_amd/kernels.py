@@ -1286,3 +1286,75 @@ def iw_accumulate(lw, terms, state, out=None, finish_k=0):
         raise RuntimeError('iw_accumulate: finish needs out [B]')
     check(_lib.lib().mvae_iw_accumulate(_ptr(lw), *args, _ptr(state), _ptr(out), Kc, B, int(finish_k), _stream()),
           'mvae_iw_accumulate')
+
+
+# ---------------------------------------------------------------------------- MultiMNIST dataset builder
+MM_DIGIT, MM_CANVAS, MM_MAX_DIGITS, MM_PLAN_STRIDE = 28, 50, 4, 17     # MVAE_MM_* of include/mvae_hip.h
+MM_WMIN, MM_WMAX, MM_KSIZE = 7, 50, 9
+_MM_TABLES = {}       # device -> (kk int32 [44, 50, 9], bounds int32 [44, 50, 2]), built once
+
+
+def multimnist_validate_plan(plan, n_bank):
+    """Host check of a compose plan (int32 [M, 17]: n, then four records (bank index, w, top, left)); returns it as a
+    contiguous int32 array.  ``ValueError`` names the first defect: the kernel is never given an out-of-range plan."""
+    import numpy as np
+    plan = np.ascontiguousarray(plan)
+    if plan.ndim != 2 or plan.shape[1] != MM_PLAN_STRIDE or plan.shape[0] < 1 or plan.dtype.kind not in 'iu':
+        raise ValueError('plan must be an integer array [M >= 1, %d], got %s %s' % (MM_PLAN_STRIDE, plan.dtype, plan.shape))
+    plan = plan.astype(np.int64)
+    if int(n_bank) < 1:
+        raise ValueError('the digit bank is empty')
+    n = plan[:, 0]
+    if ((n < 0) | (n > MM_MAX_DIGITS)).any():
+        raise ValueError('plan: digit count outside 0..%d in canvas %d' % (MM_MAX_DIGITS, int(np.argmax((n < 0) | (n > MM_MAX_DIGITS)))))
+    rec = plan[:, 1:].reshape(-1, MM_MAX_DIGITS, 4)
+    used = np.arange(MM_MAX_DIGITS)[None, :] < n[:, None]
+    ix, w, top, left = (rec[:, :, k] for k in range(4))
+    for bad, what in (((ix < 0) | (ix >= int(n_bank)), 'bank index outside 0..%d' % (int(n_bank) - 1)),
+                      ((w < MM_WMIN) | (w > MM_WMAX), 'width outside %d..%d' % (MM_WMIN, MM_WMAX)),
+                      ((top < 0) | (top + w > MM_CANVAS), 'rows top..top+w outside the %d-pixel canvas' % MM_CANVAS),
+                      ((left < 0) | (left + w > MM_CANVAS), 'columns left..left+w outside the %d-pixel canvas' % MM_CANVAS)):
+        bad = bad & used
+        if bad.any():
+            m, d = np.argwhere(bad)[0]
+            raise ValueError('plan: %s (canvas %d, digit %d: index %d, w %d, top %d, left %d)'
+                             % (what, m, d, ix[m, d], w[m, d], top[m, d], left[m, d]))
+    return plan.astype(np.int32)
+
+
+def _multimnist_tables(device):
+    """The fixed-point BILINEAR tables of 28 -> w for every supported width, zero-padded to one shape."""
+    import numpy as np
+    key = (device.type, device.index)
+    if key not in _MM_TABLES:
+        from .preprocess import _axis_tables
+        kk = np.zeros((MM_WMAX - MM_WMIN + 1, MM_CANVAS, MM_KSIZE), dtype=np.int32)
+        bounds = np.zeros((MM_WMAX - MM_WMIN + 1, MM_CANVAS, 2), dtype=np.int32)
+        for w in range(MM_WMIN, MM_WMAX + 1):
+            k, b, ks = _axis_tables(MM_DIGIT, w)
+            if ks > MM_KSIZE or int((b[:, 0] + b[:, 1]).max()) > MM_DIGIT or int(b[:, 1].max()) > ks:
+                raise RuntimeError('resample table of 28 -> %d does not fit the compose kernel' % w)
+            kk[w - MM_WMIN, :w, :ks] = k
+            bounds[w - MM_WMIN, :w] = b
+        _MM_TABLES[key] = (torch.from_numpy(kk).to(device), torch.from_numpy(bounds).to(device))
+    return _MM_TABLES[key]
+
+
+def multimnist_compose(bank, plan):
+    """Compose ``M`` MultiMNIST canvases in one launch (mvae_multimnist_compose).  ``bank``: uint8 [n_bank, 28, 28] on
+    the GPU; ``plan``: host integer array [M, 17] (see ``multimnist_validate_plan`` -- validated here, on the host,
+    before anything else).  Returns (canvas uint8 [M, 50, 50], flags int32 [M]) on the GPU: flags is 1 where a pixel
+    sum exceeded 255, and the canvas holds min(sum, 255)."""
+    if bank.dim() != 3 or tuple(bank.shape[1:]) != (MM_DIGIT, MM_DIGIT) or bank.dtype != torch.uint8:
+        raise ValueError('bank must be uint8 [n_bank, 28, 28], got %s %s' % (bank.dtype, tuple(bank.shape)))
+    plan = multimnist_validate_plan(plan, bank.shape[0])
+    _need_gpu(bank)
+    bank = bank.contiguous()
+    M = plan.shape[0]
+    canvas = torch.empty(M, MM_CANVAS, MM_CANVAS, dtype=torch.uint8, device=bank.device)
+    flags = torch.empty(M, dtype=torch.int32, device=bank.device)
+    kk, bounds = _multimnist_tables(bank.device)
+    plan_dev = torch.from_numpy(plan).to(bank.device)
+    check(_lib.lib().mvae_multimnist_compose(_ptr(bank), int(bank.shape[0]), _ptr(plan_dev), M, _ptr(kk), _ptr(bounds),
+                                             _ptr(canvas), _ptr(flags), _stream()), 'mvae_multimnist_compose')
+    return canvas, flags

@@ -1,1 +1,3 @@
 from . import model  # noqa: F401
+from . import utils  # noqa: F401
+from . import datasets  # noqa: F401

@@ -39,6 +39,7 @@ from ..base import ProductOfExpertsB as ProductOfExperts, prior_expert  # noqa: 
 from ..layers import Swish  # noqa: F401
 
 max_length = 4          # multimnist/utils.py:12
+all_characters = '0123456789'
 n_characters = 12       # 10 digits + SOS + FILL (multimnist/utils.py:13-19)
 SOS, FILL = 10, 11
 KEEP = 0.9              # nn.GRU(..., dropout=0.1) between the decoder's two layers

@@ -6,8 +6,9 @@ fused or captured MultiMNIST step.
 
     python multimodal-vae-public_amd/multimnist/train.py --cuda --synthetic
 
-The MultiMNIST dataset builder (multimnist/datasets.py) is not part of this repository yet: without ``--synthetic``
-the script says so and exits."""
+Without ``--synthetic`` the batches come from ``<data-dir>/multimnist/{training,test}.pt`` through
+``datasets.MultiMNISTLoader`` (the split resident in HBM, ToTensor on the device).  The data set does not exist until
+it is built: when the files are missing the script names the dataset builder's command and exits."""
 import os
 import sys
 
@@ -91,8 +92,12 @@ def parser():
 def main(argv=None):
     args = parser().parse_args(argv)
     if not args.synthetic:
-        raise SystemExit('the MultiMNIST dataset builder (multimnist/datasets.py) is not part of this repository yet: '
-                         'run with --synthetic')
+        from .datasets import MultiMNIST
+        folder = os.path.join(args.data_dir, MultiMNIST.processed_folder)
+        if not all(os.path.exists(os.path.join(folder, f)) for f in (MultiMNIST.training_file, MultiMNIST.test_file)):
+            raise SystemExit('no MultiMNIST files under %s: run the dataset builder first (python %s --data-dir %s), '
+                             'or run with --synthetic'
+                             % (folder, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'datasets.py'), args.data_dir))
     args.cuda = args.cuda and torch.cuda.is_available()
     if not args.cuda:
         raise SystemExit('this drop-in runs the MVAE step as HIP kernels: pass --cuda on a ROCm GPU box '
@@ -101,8 +106,13 @@ def main(argv=None):
     torch.cuda.set_device(device)
     if not os.path.isdir(args.out_dir):
         os.makedirs(args.out_dir)
-    train_loader = SyntheticLoader(args.batch_size, args.steps_per_epoch, 1234, device, last_batch=args.synthetic_last_batch)
-    test_loader = SyntheticLoader(args.batch_size, max(1, args.steps_per_epoch // 10), 4321, device)
+    if args.synthetic:
+        train_loader = SyntheticLoader(args.batch_size, args.steps_per_epoch, 1234, device, last_batch=args.synthetic_last_batch)
+        test_loader = SyntheticLoader(args.batch_size, max(1, args.steps_per_epoch // 10), 4321, device)
+    else:
+        from .datasets import MultiMNISTLoader
+        train_loader = MultiMNISTLoader(args.data_dir, True, args.batch_size, True, device, seed=1234)
+        test_loader = MultiMNISTLoader(args.data_dir, False, args.batch_size, False, device)
     N_mini_batches = len(train_loader)
 
     model = MVAE(args.n_latents)

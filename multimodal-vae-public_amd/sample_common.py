@@ -92,6 +92,16 @@ def posterior(model, image=None, label=None):
 def generate(model, n_samples, mu, std, eps=None):
     """z = eps * std + mu for ``n_samples`` draws (mnist/sample.py:102-109), decoded by both
     decoders.  Returns (z, image probabilities, label logits)."""
+    return _generate(model, model.label_decoder, n_samples, mu, std, eps)
+
+
+def generate_text(model, n_samples, mu, std, eps=None):
+    """``generate`` for the MultiMNIST MVAE, whose second decoder is ``text_decoder`` (multimnist/sample.py:119-129):
+    returns (z, image probabilities, character logits [n, 4, n_characters])."""
+    return _generate(model, model.text_decoder, n_samples, mu, std, eps)
+
+
+def _generate(model, label_decoder, n_samples, mu, std, eps):
     dev = next(model.parameters()).device
     if eps is None:
         eps = torch.randn(n_samples, model.n_latents)
@@ -102,7 +112,7 @@ def generate(model, n_samples, mu, std, eps=None):
         logits = model.image_decoder(z).contiguous()
         img = torch.empty_like(logits)
         K.sigmoid_fwd(logits, img)                                                     # F.sigmoid, mnist/sample.py:111
-        lbl = model.label_decoder(z)
+        lbl = label_decoder(z)
     return z, img, lbl
 
 
