@@ -846,6 +846,41 @@ int mvae_multimnist_compose(const uint8_t *bank, int n_bank, const int *plan_dev
                             const int *bounds_dev, uint8_t *canvas, int *flags, mvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * K22  Segmented BCE-with-logits row sums (csrc/loss_multi.hip): the reconstruction terms of SEVERAL image
+ *      modalities in one launch -- vision/train.py:20-58,61-73 sums six image BCEs per ELBO term and :183-288
+ *      evaluates seven terms per step.  For up to MVAE_BCE_MULTI_MAX segments (logits matrices of R rows each):
+ *        rowsum[r] = sum_s weight_s * sum_p bce(logits_s[r, p], target_s[r % target_rows, p])
+ *        dlogits_s[r, p] = drow[r / rows_per_group] * weight_s * dbce/dx        (drow is a DEVICE array)
+ *      with the bce of K11.  A row's elements are cut into chunks of 4096 across blocks (the grid follows the bytes,
+ *      not R); each block leaves one weighted partial in `ws`, and a second small launch adds a row's partials in
+ *      index order: no atomics, the same inputs give the same bits.  float4 loads where P % 4 == 0 and the segment's
+ *      pointers are 16-byte aligned, scalar loads otherwise (decided per segment).
+ *   fwd   writes rowsum (nullable) and, for every segment with dlogits where drow_dev is given, the gradient in the
+ *         same pass.  ws: mvae_bce_multi_ws_bytes(segs, n_segs, R) bytes (R * chunks-per-row floats), read and
+ *         written only when rowsum is given.
+ *   bwd   the gradient alone, the same arithmetic (bit-equal to the fused one); segments without dlogits are skipped.
+ *   mvae_bce_multi_ws_bytes is a host-only function of the P's and R (pointers are only compared with NULL); 0 for
+ *         a table the launches refuse.
+ *   Refused on the host before any launch: a null table, a null logits / target, n_segs outside 1..8, P <= 0,
+ *   R <= 0, rows_per_group <= 0 or R % rows_per_group != 0, target_rows <= 0, nothing to write (no rowsum and no
+ *   gradient), R * chunks-per-row >= 2^31 -- MVAE_ERR_ARG; scratch too small -- MVAE_ERR_WS.
+ * ------------------------------------------------------------------------------------ */
+#define MVAE_BCE_MULTI_MAX 8
+typedef struct {
+    const float *logits;   /* [R, P] contiguous */
+    const float *target;   /* [target_rows, P] contiguous; row of logits row r is r % target_rows */
+    float *dlogits;        /* [R, P] or NULL: no gradient for this segment */
+    int P;
+    float weight;
+} mvae_bce_seg;
+size_t mvae_bce_multi_ws_bytes(const mvae_bce_seg *segs, int n_segs, int R);
+int mvae_bce_multi_fwd(const mvae_bce_seg *segs, int n_segs, float *rowsum /* nullable */,
+                       const float *drow_dev /* nullable */, int R, int rows_per_group, int target_rows,
+                       void *ws, size_t ws_bytes, mvae_stream_t stream);
+int mvae_bce_multi_bwd(const mvae_bce_seg *segs, int n_segs, const float *drow_dev, int R, int rows_per_group,
+                       int target_rows, mvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * C1  Gradient exchange of data-parallel replicas -- RCCL over xGMI.
  *     The reference has NO counterpart: it is single-process, single-device (no DataParallel, no
  *     torch.distributed anywhere; README.md:47 `CUDA_VISIBLE_DEVICES=0`).  What this replaces is what N

@@ -83,6 +83,13 @@ class RepackItem(ctypes.Structure):         # mvae_repack_item
 REPACK_MAX = 16
 
 
+class BceSeg(ctypes.Structure):             # mvae_bce_seg
+    _fields_ = [('logits', c_void_p), ('target', c_void_p), ('dlogits', c_void_p), ('P', c_int), ('weight', c_float)]
+
+
+BCE_MULTI_MAX = 8
+
+
 class ExpertGrads(ctypes.Structure):
     _fields_ = [('dmu', c_void_p * MAX_EXPERTS), ('dlogvar', c_void_p * MAX_EXPERTS)]
 
@@ -208,6 +215,10 @@ _SIGNATURES = {
     'mvae_iw_accumulate': (c_int, [P, P, c_int, P, c_int, P, P, c_int, c_int, c_int, P]),
     # K21: the MultiMNIST dataset builder's compose step
     'mvae_multimnist_compose': (c_int, [P, c_int, P, c_int, P, P, P, P, P]),
+    # K22: the BCE row sums of several image modalities in one launch
+    'mvae_bce_multi_ws_bytes': (c_size_t, [ctypes.POINTER(BceSeg), c_int, c_int]),
+    'mvae_bce_multi_fwd': (c_int, [ctypes.POINTER(BceSeg), c_int, P, P, c_int, c_int, c_int, P, c_size_t, P]),
+    'mvae_bce_multi_bwd': (c_int, [ctypes.POINTER(BceSeg), c_int, P, c_int, c_int, c_int, P]),
     # C1: the gradient exchange (RCCL bound at run time)
     'mvae_comm_use_library': (c_int, [ctypes.c_char_p]),
     'mvae_comm_rccl_version': (c_int, []),

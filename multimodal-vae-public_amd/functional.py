@@ -8,6 +8,7 @@ the latent path of ``MVAE.forward``.  Every ``Function`` is a thin shell over HI
     elbo_loss (bimodal, attributes)   celeba/train.py:22-65
     elbo_loss (N-modal lists)         celeba19/train.py:26-60
     elbo_loss (bimodal, digit string) multimnist/train.py:22-68
+    elbo_loss (six image modalities)  vision/train.py:20-58
 
 The fused train step (``engine.py``) does not go through these: it launches the same kernels
 directly with the loss gradient folded into the forward pass.
@@ -387,3 +388,90 @@ def elbo_loss_text(recon_image, image, recon_text, text, mu, logvar,
         rows.append(_CeRowsFn.apply(logits, labels)); weights.append(float(lambda_text))
     rows.append(_KlRowsFn.apply(mu, logvar)); weights.append(_w(annealing_factor))
     return _WeightedSumsFn.apply(weights, B, *rows)
+
+
+# ----------------------------------------------------------------------------- vision: six image modalities
+class _BceMultiRowsFn(torch.autograd.Function):
+    """rows[r] = sum_s w_s * sum_p bce(x_s[r, p], t_s[r % target_rows, p]) over up to 8 logits matrices of R rows each:
+    ONE ``mvae_bce_multi_fwd`` launch forward, ONE ``mvae_bce_multi_bwd`` backward (csrc/loss_multi.hip).  The targets
+    may hold fewer rows than the logits (the seven ELBO terms of a vision step share one batch of targets)."""
+
+    @staticmethod
+    def forward(ctx, cfg, *xs):
+        targets, weights = cfg
+        rows = torch.empty(xs[0].shape[0], dtype=torch.float32, device=xs[0].device)
+        K.bce_multi_fwd([(x, t, None, w) for x, t, w in zip(xs, targets, weights)], rows, rows_per_group=1)
+        ctx.cfg = cfg
+        ctx.save_for_backward(*xs)
+        return rows
+
+    @staticmethod
+    def backward(ctx, g):
+        targets, weights = ctx.cfg
+        xs = ctx.saved_tensors
+        dxs = [torch.empty_like(x) if ctx.needs_input_grad[i + 1] else None for i, x in enumerate(xs)]
+        if any(d is not None for d in dxs):
+            K.bce_multi_bwd([(x, t, d, w) for x, t, d, w in zip(xs, targets, dxs, weights)], g.contiguous(),
+                            rows_per_group=1)
+        return (None,) + tuple(dxs)
+
+
+N_VISION_MODALITIES = 6          # vision/datasets.py N_MODALITIES: the divisor of vision/train.py:57
+
+
+def vision_bce_rows(recons, targets):
+    """The BCE / 6 of vision/train.py:22-57 for the (recon, target) pairs given (both not None), as [R] row sums; a
+    recon may hold several groups of the target's rows (R = G * B).  None when no pair is present."""
+    xs, ts = [], []
+    for recon, target in zip(recons, targets):
+        if recon is None or target is None:
+            continue
+        n = target[0].numel()
+        x, t = recon.reshape(-1, n).contiguous(), target.reshape(-1, n).contiguous()
+        if x.shape[1:] != t.shape[1:] or x.shape[0] % t.shape[0] != 0 or (xs and x.shape[0] != xs[0].shape[0]):
+            raise ValueError("Target size ({}) must be the same as input size ({})".format(t.size(), x.size()))
+        xs.append(x); ts.append(t)
+    if not xs:
+        return None
+    if any(t.shape[0] != ts[0].shape[0] for t in ts):
+        raise ValueError('the targets of one elbo_loss call must share a batch size')
+    return _BceMultiRowsFn.apply((ts, [1.0 / N_VISION_MODALITIES] * len(xs)), *xs)
+
+
+def elbo_loss_vision(recon_image, image, recon_gray, gray, recon_edge, edge, recon_mask, mask,
+                     recon_obscured, obscured, recon_watermark, watermark, mu, logvar, annealing_factor=1.):
+    """vision/train.py:20-58 with the signature repaired (the reference's names ``recon_rotated, rotated`` while its
+    body reads ``recon_watermark, watermark``): ELBO = mean(BCE / 6 + annealing_factor * KLD), BCE the sum of the image
+    BCEs of the pairs that are both given.  All present pairs are ONE segmented row-sum launch."""
+    _need_gpu(mu)
+    bce = vision_bce_rows((recon_image, recon_gray, recon_edge, recon_mask, recon_obscured, recon_watermark),
+                          (image, gray, edge, mask, obscured, watermark))
+    rows, weights = [], []
+    if bce is not None:
+        if bce.shape[0] != mu.shape[0]:
+            raise ValueError('reconstructions of %d rows for %d latent rows' % (bce.shape[0], mu.shape[0]))
+        rows.append(bce); weights.append(1.0)
+    rows.append(_KlRowsFn.apply(mu, logvar)); weights.append(_w(annealing_factor))
+    return _WeightedMeanFn.apply(weights, *rows)
+
+
+class _GroupMeansFn(torch.autograd.Function):
+    """(total, terms): terms[g] = sum_i (w_i / B) * sum(rows_i[g * B:(g + 1) * B]) for G groups of B rows, total their
+    sum -- the G ``elbo_loss`` means of a batched step and their sum in one launch per row vector."""
+
+    @staticmethod
+    def forward(ctx, weights, G, *rows):
+        B = rows[0].numel() // G
+        dev = rows[0].device
+        out = torch.empty(G + 1, dtype=torch.float32, device=dev)
+        coefs = _coef_tensor(weights, B, dev)
+        for i, r in enumerate(rows):
+            K.group_sums(r.contiguous(), coefs[i:i + 1].expand(G).contiguous(), out[:G], out[G:], G, B, accumulate=(i > 0))
+        ctx.coefs, ctx.n = coefs, G * B
+        terms = out[:G]
+        ctx.mark_non_differentiable(terms)
+        return out[G], terms
+
+    @staticmethod
+    def backward(ctx, g, _):
+        return (None, None) + tuple((g * ctx.coefs[i]).expand(ctx.n) for i in range(ctx.coefs.numel()))

@@ -846,6 +846,46 @@ def bce_rowsum_bwd(logits, target, drow, dlogits, colw=None, rows_per_group=None
                                          target_div, t_rs, t_cs, _stream()), 'mvae_bce_rowsum_bwd')
 
 
+def _bce_segs(segs, R):
+    """[(logits [R,P], target [target_rows,P], dlogits [R,P] or None, weight)] -> (mvae_bce_seg table, target_rows)"""
+    if not 0 < len(segs) <= _lib.BCE_MULTI_MAX:
+        raise RuntimeError('1..%d BCE segments per launch' % _lib.BCE_MULTI_MAX)
+    arr = (_lib.BceSeg * len(segs))()
+    target_rows = segs[0][1].shape[0]
+    for s, (logits, target, dlogits, weight) in enumerate(segs):
+        _need_gpu(logits, target, dlogits); _f32c(logits, target, dlogits)
+        P = logits.shape[-1]
+        if logits.dim() != 2 or logits.shape[0] != R or tuple(target.shape) != (target_rows, P) or (
+                dlogits is not None and dlogits.shape != logits.shape):
+            raise RuntimeError('BCE segment %d: logits %s, target %s, dlogits %s for R = %d, target_rows = %d'
+                               % (s, tuple(logits.shape), tuple(target.shape),
+                                  None if dlogits is None else tuple(dlogits.shape), R, target_rows))
+        arr[s] = _lib.BceSeg(_ptr(logits), _ptr(target), _ptr(dlogits), int(P), float(weight))
+    return arr, target_rows
+
+
+def bce_multi_fwd(segs, rowsum, drow=None, rows_per_group=None):
+    """rowsum[r] = sum_s weight_s * sum_p bce(logits_s[r,p], target_s[r % target_rows, p]) for the segments
+    [(logits, target, dlogits or None, weight)] in ONE launch (+ the small launch that adds the partials); with
+    ``drow`` [R / rows_per_group] the segments that carry ``dlogits`` get their gradient in the same pass."""
+    R = segs[0][0].shape[0]
+    arr, target_rows = _bce_segs(segs, R)
+    _need_gpu(rowsum, drow); _f32c(rowsum, drow)
+    nbytes = _lib.lib().mvae_bce_multi_ws_bytes(arr, len(segs), R)
+    ws, ws_bytes = _ws_args(nbytes, segs[0][0].device)
+    check(_lib.lib().mvae_bce_multi_fwd(arr, len(segs), _ptr(rowsum), _ptr(drow), R, rows_per_group or R, target_rows,
+                                        ws, ws_bytes, _stream()), 'mvae_bce_multi_fwd')
+
+
+def bce_multi_bwd(segs, drow, rows_per_group=None):
+    """The gradient of ``bce_multi_fwd`` alone: dlogits_s[r,p] = drow[r / rows_per_group] * weight_s * dbce/dx."""
+    R = segs[0][0].shape[0]
+    arr, target_rows = _bce_segs(segs, R)
+    _need_gpu(drow); _f32c(drow)
+    check(_lib.lib().mvae_bce_multi_bwd(arr, len(segs), _ptr(drow), R, rows_per_group or R, target_rows, _stream()),
+          'mvae_bce_multi_bwd')
+
+
 def ce_fwd(logits, label, row, drow=None, dlogits=None, rows_per_group=None, label_rows=None):
     _need_gpu(logits, label, row, drow, dlogits); _f32c(logits, row, drow, dlogits)
     if label.dtype != torch.int64 or not label.is_contiguous():

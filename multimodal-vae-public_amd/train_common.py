@@ -62,11 +62,13 @@ _CELEBA = dict(n_latents=(100, '100'), epochs=(100, '100'), annealing=(20, '20')
 
 def _reference_flags(kind):
     d = _SMALL if kind in ('mnist', 'fashionmnist', 'multimnist') else _CELEBA      # multimnist/train.py:144-161
+    if kind == 'vision':                                                            # vision/train.py:114-127
+        d = dict(_CELEBA, n_latents=(250, '250'))
     label = 'text' if kind in ('mnist', 'fashionmnist', 'multimnist') else 'attrs'
     label_words = 'text' if label == 'text' else 'attributes'
     flags = [
         ('--n-latents', int, d['n_latents'], None, 'size of the latent embedding'),
-        ('--batch-size', int, (100, '100'), 'N', 'input batch size for training'),
+        ('--batch-size', int, (50, '50') if kind == 'vision' else (100, '100'), 'N', 'input batch size for training'),
         ('--epochs', int, d['epochs'], 'N', 'number of epochs to train'),
         ('--annealing-epochs', int, d['annealing'], 'N', 'number of epochs to anneal KL for'),
         ('--lr', float, d['lr'], 'LR', 'learning rate'),
@@ -74,6 +76,8 @@ def _reference_flags(kind):
     ]
     if kind == 'celeba19':
         flags.append(('--approx-m', int, (1, '1'), None, 'number of ELBO terms to approx. the full MVAE objective'))
+    if kind == 'vision':        # "we use lambda_i = 1 for all i" (vision/train.py:56): no lambda flags
+        return flags
     flags += [
         ('--lambda-image', float, (1., '1'), None, 'multipler for image reconstruction'),
         ('--lambda-%s' % label, float, (10., '10'), None, 'multipler for %s reconstruction' % label_words),
