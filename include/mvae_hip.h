@@ -881,6 +881,29 @@ int mvae_bce_multi_bwd(const mvae_bce_seg *segs, int n_segs, const float *drow_d
                        int target_rows, mvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * K23  The vision experiment's input pipeline (csrc/vision_data.hip): what vision/datasets.py:54-91 does per item on
+ *      the CPU, for a batch of raw uint8 sources resident in HBM, in ONE launch -- six float32 NCHW batches.
+ *   rgb [B, H, W, 3], edge / mask [B, H, W], gray [B, H, W] or NULL (then gray is the luma of rgb, Pillow's
+ *   convert('L'): (R * 19595 + G * 38470 + B * 7471 + 0x8000) >> 16), mark [H, W, 4]: the RGBA watermark already resized
+ *   to H x W, one for the batch.  All uint8, contiguous; no alignment is required of any of them.
+ *   image_out / obscured_out / watermark_out [B, 3, S, S], gray_out / edge_out / mask_out [B, 1, S, S].
+ *     obscured  = rgb where x <= W / 2, else 0                                          (vision/datasets.py:108-109)
+ *     watermark = Pillow's paste(mark, (0, 0), mark) on rgb: per channel t = dst * (255 - a) + src * a + 128,
+ *                 ((t >> 8) + t) >> 8 with a the mark's alpha                                         (:125-128)
+ *   Then every plane takes Resize + CenterCrop + ToTensor exactly as mvae_resize_crop_u8_to_f32 (same tables, same
+ *   meaning of out_h / out_w, crop_top / crop_left, [y0, y1)); mask_out holds 1.0f - u8 / 255.0f (:87).
+ *   Grid (B, 4): a block owns three planes (image | obscured | watermark | gray, edge, mask) and reads each source
+ *   byte once; (y1 - y0) * S * 3 bytes of LDS plus 32 KiB of staged rows, <= 150 KiB.  No atomics, no scratch.
+ *   Refused on the host before any launch (MVAE_ERR_ARG): a null pointer other than gray, a non-positive size, a crop
+ *   outside the resized image, [y0, y1) outside the image or empty, an LDS need above 150 KiB.
+ * ------------------------------------------------------------------------------------ */
+int mvae_vision_compose(const uint8_t *rgb, const uint8_t *edge, const uint8_t *mask, const uint8_t *gray /* nullable */,
+                        const uint8_t *mark, float *image_out, float *gray_out, float *edge_out, float *mask_out,
+                        float *obscured_out, float *watermark_out, int B, int H, int W, int out_h, int out_w, int S,
+                        int crop_top, int crop_left, const int *kx_dev, const int *bx_dev, int ksx, const int *ky_dev,
+                        const int *by_dev, int ksy, int y0, int y1, mvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * C1  Gradient exchange of data-parallel replicas -- RCCL over xGMI.
  *     The reference has NO counterpart: it is single-process, single-device (no DataParallel, no
  *     torch.distributed anywhere; README.md:47 `CUDA_VISIBLE_DEVICES=0`).  What this replaces is what N

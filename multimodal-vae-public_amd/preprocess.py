@@ -3,6 +3,7 @@
     ToTensor                      (mnist/train.py:160,164)        -> ``to_tensor(u8)``
     Compose([Resize(64), CenterCrop(64), ToTensor()])
                                   (celeba/train.py:146-148)       -> ``ResizeCenterCropToTensor(64)(u8_nhwc)``
+    the six modalities of one item  (vision/datasets.py:54-91)    -> ``VisionCompose(64)(rgb, edge, mask, mark, gray)``
 
 Input: raw ``uint8`` images already in HBM (``[B, H, W]`` / ``[B, H, W, 3]``, the decoded JPEG / IDX
 bytes); output: the ``float32`` NCHW batch the MVAE step consumes.  Resize is byte-exact with Pillow's
@@ -86,3 +87,51 @@ class ResizeCenterCropToTensor(object):
                                                     _ptr(bx), ksx, _ptr(ky), _ptr(by), ksy, y0, y1, _stream()),
               'mvae_resize_crop_u8_to_f32')
         return out
+
+
+class VisionCompose(object):
+    """The six modalities of the vision step (``vision.model.MODALITIES`` order: image, gray, edge, mask, obscured,
+    watermark) from one batch of raw uint8 sources, in ONE launch: the right half blacked out, the watermark pasted, and
+    ``Compose([Resize(size), CenterCrop(size), ToTensor()])`` on all six, ``1 - x`` for the mask (vision/datasets.py:
+    43-45, 64-87, 97-129).  ``rgb`` [B, H, W, 3], ``edge`` / ``mask`` / ``gray`` [B, H, W], ``mark`` [H, W, 4]: the RGBA
+    watermark already resized to the images' size.  Without ``gray`` the kernel takes the luma of ``rgb`` (Pillow's
+    ``convert('L')``)."""
+
+    def __init__(self, size=64):
+        self.size = int(size)
+        self._resize = ResizeCenterCropToTensor(self.size)      # its per-(H, W, device) plan cache, unchanged
+
+    def __call__(self, rgb, edge, mask, mark, gray=None):
+        named = [('rgb', rgb, 4), ('edge', edge, 3), ('mask', mask, 3), ('mark', mark, 3)]
+        if gray is not None:
+            named.append(('gray', gray, 3))
+        for name, t, rank in named:
+            if not torch.is_tensor(t) or t.dtype != torch.uint8:
+                raise TypeError('%s: expected a uint8 tensor, got %s' % (name, getattr(t, 'dtype', type(t))))
+            if t.dim() != rank:
+                raise ValueError('%s: expected %d dimensions, got shape %s' % (name, rank, tuple(t.shape)))
+        if rgb.shape[3] != 3:
+            raise ValueError('rgb: expected [B, H, W, 3], got %s' % (tuple(rgb.shape),))
+        B, H, W, _ = rgb.shape
+        if B <= 0:
+            raise ValueError('rgb: an empty batch')
+        for name, t, _ in named[1:]:
+            want = (H, W, 4) if name == 'mark' else (B, H, W)
+            if tuple(t.shape) != want:
+                raise ValueError('%s: expected %s to go with rgb %s, got %s' % (name, want, tuple(rgb.shape),
+                                                                                tuple(t.shape)))
+        tensors = [t for _, t, _ in named]
+        _need_gpu(*tensors)
+        if any(t.device != rgb.device for t in tensors):
+            raise ValueError('the sources are on different devices')
+        rgb, edge, mask, mark = [t.contiguous() for t in (rgb, edge, mask, mark)]
+        gray = gray.contiguous() if gray is not None else None
+        nh, nw, top, left, ksx, ksy, y0, y1, (kx, bx, ky, by) = self._resize._plan(H, W, rgb.device)
+        S = self.size
+        out = [torch.empty(B, c, S, S, dtype=torch.float32, device=rgb.device) for c in (3, 1, 1, 1, 3, 3)]
+        check(_lib.lib().mvae_vision_compose(_ptr(rgb), _ptr(edge), _ptr(mask), _ptr(gray), _ptr(mark),
+                                             *([_ptr(o) for o in out] +
+                                               [B, H, W, nh, nw, S, top, left, _ptr(kx), _ptr(bx), ksx, _ptr(ky),
+                                                _ptr(by), ksy, y0, y1, _stream()])),
+              'mvae_vision_compose')
+        return tuple(out)

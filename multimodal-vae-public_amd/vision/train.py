@@ -22,8 +22,10 @@ launch for the seven terms, each decoder once on 7B rows, ONE segmented BCE laun
 selects one; ``fused`` is the default because it measured faster (9.9 against 28.5 ms per step at B = 50, D = 250:
 profiles/vision_step.txt).
 
-``vision/datasets.py`` (Canny edges, dlib face masks) is out of scope: without ``--synthetic`` the script says so and
-exits."""
+Without ``--synthetic`` the loaders are ``datasets.CelebVisionLoader`` over ``--data-dir`` ('train' shuffled, 'val' not;
+vision/train.py:138-144) with the watermark of ``--watermark-file``.  The edge and mask folders it reads are written by the
+reference's ``vision/setup.py`` (Canny edges, dlib face masks), which is out of scope here: when they are missing the script
+says so and exits."""
 import os
 import sys
 
@@ -185,14 +187,29 @@ def parser():
     p.add_argument('--step', choices=sorted(STEPS), default=DEFAULT_STEP,
                    help="'eager': the reference's loop body, seven model() calls; 'fused': the same step batched "
                         "[default: %s]" % DEFAULT_STEP)
+    p.add_argument('--watermark-file', type=str, default='./watermark.png',
+                   help='the image with an alpha channel pasted onto the colour image for the watermark modality '
+                        '[default: ./watermark.png]')
     return p
+
+
+def check_data(args):
+    """Without --synthetic: exit with what is missing under --data-dir, or when --watermark-file is."""
+    from .datasets import missing_data
+    missing = missing_data(args.data_dir)
+    if missing:
+        raise SystemExit('the vision data set is not under --data-dir %s: missing %s.  Building the edge / mask folders '
+                         '(vision/setup.py: scikit-image Canny edges, dlib face masks) is out of scope here: run the '
+                         "reference's setup.py first, or run with --synthetic" % (args.data_dir, ', '.join(missing)))
+    if not os.path.isfile(args.watermark_file):
+        raise SystemExit('the watermark image %s is missing: name one with --watermark-file (an image with an alpha '
+                         'channel), or run with --synthetic' % args.watermark_file)
 
 
 def main(argv=None):
     args = parser().parse_args(argv)
     if not args.synthetic:
-        raise SystemExit('the vision data set (vision/datasets.py: Canny edges, dlib face masks, watermarks) is out of '
-                         'scope here: run with --synthetic')
+        check_data(args)
     args.cuda = args.cuda and torch.cuda.is_available()
     if not args.cuda:
         raise SystemExit('this drop-in runs the MVAE step as HIP kernels: pass --cuda on a ROCm GPU box '
@@ -203,8 +220,19 @@ def main(argv=None):
     for d in [args.out_dir, results] + [os.path.join(results, m) for m in MODALITIES]:
         if not os.path.isdir(d):
             os.makedirs(d)
-    train_loader = SyntheticLoader(args.batch_size, args.steps_per_epoch, 1234, device)
-    test_loader = SyntheticLoader(args.batch_size, max(1, args.steps_per_epoch // 10), 4321, device)
+    if args.synthetic:
+        train_loader = SyntheticLoader(args.batch_size, args.steps_per_epoch, 1234, device)
+        test_loader = SyntheticLoader(args.batch_size, max(1, args.steps_per_epoch // 10), 4321, device)
+    else:
+        from .datasets import CelebVisionLoader
+        train_loader = CelebVisionLoader('train', args.data_dir, args.batch_size, True, device, seed=1234,
+                                         watermark_path=args.watermark_file)
+        test_loader = CelebVisionLoader('val', args.data_dir, args.batch_size, False, device,
+                                        watermark_path=args.watermark_file)
+        for name, loader in (('train', train_loader), ('val', test_loader)):
+            if len(loader) == 0:
+                raise SystemExit('%s lists no image of the %r partition'
+                                 % (os.path.join(args.data_dir, 'Eval/list_eval_partition.txt'), name))
     N_mini_batches = len(train_loader)
 
     model = MVAE(args.n_latents, use_cuda=True)
