@@ -904,6 +904,37 @@ int mvae_vision_compose(const uint8_t *rgb, const uint8_t *edge, const uint8_t *
                         const int *by_dev, int ksy, int y0, int y1, mvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * K24  Importance-weighted estimates of several image modalities from one decoder pass (csrc/loglike_multi.hip): the
+ *      vision experiment's evaluation wants the six marginals log p(x_m) and the joint log p(x_1..x_6) of a datum from
+ *      the same K draws.  K20's accumulate folds ONE state from at most two reconstruction rows and K22 returns only
+ *      the weighted sum over its segments; here up to MVAE_BCE_MULTI_MAX segments (mvae_bce_seg: logits [R, P_s] on the
+ *      R = Kc * B sample-major rows of mvae_iw_draw, target [B, P_s], row r reads target row r % B; dlogits and weight
+ *      are ignored) give S + 1 states in two launches:
+ *        rec_s[k, b]  = sum_p bce(logits_s[k * B + b, p], target_s[b, p])                 (the bce of K11)
+ *        logw_s[k, b] = lw[k, b] - rec_s[k, b]                       s = 0 .. S-1         (the marginals)
+ *        logw_S[k, b] = lw[k, b] - (rec_0 + rec_1 + ... + rec_{S-1})[k, b], added in segment order    (the joint)
+ *        state[j, b]  = (running maximum, running sum of exp(logw_j - maximum)) over k,   state [S + 1, B, 2]
+ *        out[j, b]    = maximum + log(sum) - log(finish_k)           when finish_k > 0,   out [S + 1, B]
+ *   score   K22's plan: a row's elements are cut into chunks of 4096, one block per (row, chunk), one unweighted
+ *           partial per block in `ws`; float4 loads where P % 4 == 0 and the segment's pointers are 16-byte aligned,
+ *           scalar loads otherwise (decided per segment).
+ *   fold    one wave per (state, datum), lanes along k: a lane adds its sample's partials per segment in index order
+ *           (the per-segment row sums never exist as an array), forms its log-weight, and the wave merges it into the
+ *           state by K20's rules: the caller initialises state to (-inf, 0), the maximum is subtracted before every
+ *           exp, a -inf maximum is never subtracted from itself, wave maximum then wave sum.  finish_k as in
+ *           mvae_iw_accumulate: the TOTAL number of samples folded so far, this chunk included.
+ *   No atomics: the same inputs give the same bits.  With S = 1 state 0 and state 1 hold the same bits.
+ *   mvae_iw_score_multi_ws_bytes is a host-only function of the P's and R = Kc * B (R * chunks-per-row floats); 0 for
+ *   a table the launch refuses.
+ *   Refused on the host before any launch: a null table, a null logits / target / lw / state, n_segs outside 1..8,
+ *   P <= 0, Kc <= 0, B <= 0, finish_k < 0, finish_k > 0 without out, Kc * B or R * chunks-per-row >= 2^31 --
+ *   MVAE_ERR_ARG; scratch too small -- MVAE_ERR_WS.
+ * ------------------------------------------------------------------------------------ */
+size_t mvae_iw_score_multi_ws_bytes(const mvae_bce_seg *segs, int n_segs, int R);
+int mvae_iw_score_multi(const mvae_bce_seg *segs, int n_segs, const float *lw, float *state, float *out /* nullable */,
+                        int Kc, int B, int finish_k, void *ws, size_t ws_bytes, mvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * C1  Gradient exchange of data-parallel replicas -- RCCL over xGMI.
  *     The reference has NO counterpart: it is single-process, single-device (no DataParallel, no
  *     torch.distributed anywhere; README.md:47 `CUDA_VISIBLE_DEVICES=0`).  What this replaces is what N

@@ -221,6 +221,9 @@ _SIGNATURES = {
     'mvae_bce_multi_bwd': (c_int, [ctypes.POINTER(BceSeg), c_int, P, c_int, c_int, c_int, P]),
     # K23: the six modalities of the vision step from raw uint8 sources in one launch
     'mvae_vision_compose': (c_int, [P] * 11 + [c_int] * 8 + [P, P, c_int, P, P, c_int, c_int, c_int, P]),
+    # K24: the per-modality and joint importance-weighted estimates from one decoder pass
+    'mvae_iw_score_multi_ws_bytes': (c_size_t, [ctypes.POINTER(BceSeg), c_int, c_int]),
+    'mvae_iw_score_multi': (c_int, [ctypes.POINTER(BceSeg), c_int, P, P, P, c_int, c_int, c_int, P, c_size_t, P]),
     # C1: the gradient exchange (RCCL bound at run time)
     'mvae_comm_use_library': (c_int, [ctypes.c_char_p]),
     'mvae_comm_rccl_version': (c_int, []),

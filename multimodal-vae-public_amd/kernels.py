@@ -1328,6 +1328,28 @@ def iw_accumulate(lw, terms, state, out=None, finish_k=0):
           'mvae_iw_accumulate')
 
 
+def iw_score_multi(lw, segs, state, out=None, finish_k=0):
+    """The chunk ``lw[Kc, B]`` and the segments ``[(logits [Kc * B, P_s], target [B, P_s])]`` of one decoder pass folded
+    into ``state[S + 1, B, 2]``: state s takes ``lw - rec_s`` (the marginal of segment s), state S takes ``lw - (rec_0 +
+    ... + rec_{S-1})`` (the joint), ``rec_s`` the BCE-with-logits row sums -- mvae_iw_score_multi (K24).  Start every
+    state at (-inf, 0); ``finish_k`` as in ``iw_accumulate``, with ``out`` [S + 1, B]."""
+    _need_gpu(lw, state, out); _f32c(lw, state, out)
+    segs = [tuple(sg) for sg in segs]
+    if lw.dim() != 2 or tuple(state.shape) != (len(segs) + 1, lw.shape[1], 2):
+        raise RuntimeError('iw_score_multi: lw [Kc, B] and state [S + 1, B, 2] for S segments; got %s and %s for %d'
+                           % (tuple(lw.shape), tuple(state.shape), len(segs)))
+    Kc, B = lw.shape
+    if any(len(sg) != 2 or sg[1].shape[0] != B for sg in segs):
+        raise RuntimeError('iw_score_multi: a segment is (logits [Kc * B, P], target [B, P])')
+    arr, _ = _bce_segs([(logits, target, None, 1.0) for logits, target in segs], Kc * B)
+    if finish_k and (out is None or tuple(out.shape) != (len(segs) + 1, B)):
+        raise RuntimeError('iw_score_multi: finish needs out [S + 1, B]')
+    nbytes = _lib.lib().mvae_iw_score_multi_ws_bytes(arr, len(segs), Kc * B)
+    ws, ws_bytes = _ws_args(nbytes, lw.device)
+    check(_lib.lib().mvae_iw_score_multi(arr, len(segs), _ptr(lw), _ptr(state), _ptr(out), Kc, B, int(finish_k), ws,
+                                         ws_bytes, _stream()), 'mvae_iw_score_multi')
+
+
 # ---------------------------------------------------------------------------- MultiMNIST dataset builder
 MM_DIGIT, MM_CANVAS, MM_MAX_DIGITS, MM_PLAN_STRIDE = 28, 50, 4, 17     # MVAE_MM_* of include/mvae_hip.h
 MM_WMIN, MM_WMAX, MM_KSIZE = 7, 50, 9
