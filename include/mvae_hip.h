@@ -935,6 +935,47 @@ int mvae_iw_score_multi(const mvae_bce_seg *segs, int n_segs, const float *lw, f
                         int Kc, int B, int finish_k, void *ws, size_t ws_bytes, mvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * K25  Importance-weighted estimates of many one-logit modalities from one decoder pass (csrc/loglike_heads.hip): the
+ *      CelebA-19 evaluation wants the image marginal, the 18 attribute marginals log p(a_i) and the joint of a datum from
+ *      the same K draws.  The 18 attribute decoders end in Linear(512, 1): K24 stops at MVAE_BCE_MULTI_MAX segments and
+ *      wants a logits matrix per segment, K20's accumulate folds one state per launch.  Two entry points:
+ *   heads_bce_rows  the last layer of G one-logit heads fused with its Bernoulli term, on the R = Kc * B sample-major rows
+ *                   of mvae_iw_draw:
+ *                     logit[g, r] = sum_j h[g * h_gs + r * ldh + j] * w[g * w_gs + j] + bias[g * b_gs]        j < H
+ *                     rec[g * rec_gs + r] = bce(logit[g, r], target[(r % target_rows) * ldt + g])     (the bce of K11)
+ *                     logits_out[g * logits_gs + r] = logit[g, r]                                (nullable: parity runs)
+ *                   h: the post-Swish output of the third grouped Linear, [G, R, H] with unit column stride and any
+ *                   ldh >= H.  w, bias: (pointer of group 0, group stride in floats), like the grouped Linear entry
+ *                   points.  target: float {0, 1} [target_rows, >= G] with row stride ldt; group g reads column g (a
+ *                   column range of the [B, 18] attribute matrix is passed as it is).  Grid (row blocks, G): lanes along
+ *                   H, a wave owns a row at a time, the group's weight row stays in registers across the rows of a
+ *                   block, the wave reduces in a fixed shuffle order.  float4 loads where H % 4 == 0, ldh % 4 == 0, h_gs
+ *                   and w_gs are multiples of 4 and h and w are 16-byte aligned; scalar loads otherwise (decided once per
+ *                   launch).  Every activation is read once: HBM-bound.  No atomics, no scratch: the same inputs give
+ *                   the same bits, and a row's value depends neither on R nor on the grid.
+ *                   Refused on the host before any launch (MVAE_ERR_ARG): a null h / w / bias / target / rec, G outside
+ *                   1..4096, R, H or target_rows <= 0, ldh < H, ldt < G, G * R >= 2^31.
+ *   iw_fold_rows    K24's fold for row sums that already exist, up to MVAE_IW_FOLD_MAX states besides the joint:
+ *                     logw_j[k, b] = lw[k, b] - rec[sel[j] * rec_ss + k * B + b]                      j = 0 .. S-1
+ *                     logw_S[k, b] = lw[k, b] - (rec[sel[0]..] + ... + rec[sel[S-1]..])[k, b]   added in j order
+ *                     state [S + 1, B, 2], out [S + 1, B], finish_k as in mvae_iw_accumulate
+ *                   sel: a HOST array of S row indices, passed to the kernel by value; NULL means 0 .. S-1 (a subset of
+ *                   the rows is scored without a copy; the caller answers for sel[j] * rec_ss + Kc * B lying inside rec).
+ *                   One wave per (state, datum), lanes along k, K20's rules: the caller initialises state to (-inf, 0),
+ *                   the maximum is subtracted before every exp, a -inf maximum is never subtracted from itself, wave
+ *                   maximum then wave sum, no atomics.  With S = 1 state 0 and state 1 hold the same bits.
+ *                   Refused on the host before any launch (MVAE_ERR_ARG): a null rec / lw / state, S outside 1..64, a
+ *                   negative sel entry, Kc or B <= 0, rec_ss < Kc * B, finish_k < 0, finish_k > 0 without out,
+ *                   Kc * B >= 2^31.
+ * ------------------------------------------------------------------------------------ */
+#define MVAE_IW_FOLD_MAX 64
+int mvae_heads_bce_rows(const float *h, int ldh, size_t h_gs, const float *w, size_t w_gs, const float *bias, size_t b_gs,
+                        const float *target, int target_rows, int ldt, float *rec, size_t rec_gs,
+                        float *logits_out /* nullable */, size_t logits_gs, int G, int R, int H, mvae_stream_t stream);
+int mvae_iw_fold_rows(const float *rec, size_t rec_ss, const int *sel /* host, nullable */, int S, const float *lw,
+                      float *state, float *out /* nullable */, int Kc, int B, int finish_k, mvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * C1  Gradient exchange of data-parallel replicas -- RCCL over xGMI.
  *     The reference has NO counterpart: it is single-process, single-device (no DataParallel, no
  *     torch.distributed anywhere; README.md:47 `CUDA_VISIBLE_DEVICES=0`).  What this replaces is what N

@@ -12,6 +12,8 @@ hyphen) or ``importlib.import_module('multimodal-vae-public_amd')``.
     mvae_amd.capture_step(body, example_args, model=, optimizer=)     the reference's unchanged loop body as ONE hipGraph
     mvae_amd.log_likelihood(model, image=, label=, score=, given=)    importance-weighted marginal log-likelihood
     mvae_amd.vision.loglike.log_likelihood(model, data, score=, given=)   the same for the six vision modalities + joint
+    mvae_amd.celeba19.loglike.log_likelihood(model, image=, attrs=, score=, given=)   CelebA-19: image, 18 attributes + joint
+                                                                      (``from mvae_amd.celeba19 import loglike``)
 """
 from . import _lib, kernels, arena, layers, functional, base, engine, optim, parallel, graph  # noqa: F401
 from .graph import capture_step  # noqa: F401

@@ -88,6 +88,7 @@ class BceSeg(ctypes.Structure):             # mvae_bce_seg
 
 
 BCE_MULTI_MAX = 8
+IW_FOLD_MAX = 64      # MVAE_IW_FOLD_MAX
 
 
 class ExpertGrads(ctypes.Structure):
@@ -224,6 +225,10 @@ _SIGNATURES = {
     # K24: the per-modality and joint importance-weighted estimates from one decoder pass
     'mvae_iw_score_multi_ws_bytes': (c_size_t, [ctypes.POINTER(BceSeg), c_int, c_int]),
     'mvae_iw_score_multi': (c_int, [ctypes.POINTER(BceSeg), c_int, P, P, P, c_int, c_int, c_int, P, c_size_t, P]),
+    # K25: G one-logit heads fused with their Bernoulli term, and the fold of up to IW_FOLD_MAX existing row sums
+    'mvae_heads_bce_rows': (c_int, [P, c_int, c_size_t, P, c_size_t, P, c_size_t, P, c_int, c_int, P, c_size_t, P,
+                                    c_size_t, c_int, c_int, c_int, P]),
+    'mvae_iw_fold_rows': (c_int, [P, c_size_t, ctypes.POINTER(c_int), c_int, P, P, P, c_int, c_int, c_int, P]),
     # C1: the gradient exchange (RCCL bound at run time)
     'mvae_comm_use_library': (c_int, [ctypes.c_char_p]),
     'mvae_comm_rccl_version': (c_int, []),

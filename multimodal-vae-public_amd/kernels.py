@@ -242,6 +242,25 @@ def linear_fwd_grouped(x, w0, w_gs, b0, b_gs, pre=None, act=None):
                                              ws, wsb, _stream()), 'mvae_linear_fwd_grouped')
 
 
+def linear_fwd_grouped_shared(x, G, w0, w_gs, b0, b_gs, pre=None, act=None):
+    """``linear_fwd_grouped`` for G groups that all read the SAME input ``x`` [rows, width] (unit column stride): the
+    group stride of x is 0, which is what a single group already passes -- every loader of the grouped forward forms
+    ``x + group * stride`` and only reads through it.  The outputs are [G, rows, N] as usual.  (The first layer of
+    celeba19's attribute decoders on one batch of z.)"""
+    _need_gpu(x, w0, b0, pre, act)
+    M, K = _rows2d(x, 'x').shape
+    N = w0.shape[0]
+    out = _g3(pre if pre is not None else act, 'output')
+    if out.shape[0] != int(G) or out.shape[1] != M or out.shape[2] != N:
+        raise RuntimeError('output must be [%d, %d, %d], got %s' % (G, M, N, tuple(out.shape)))
+    if pre is not None and act is not None and (act.stride() != pre.stride()):
+        raise RuntimeError('pre and act must share a layout')
+    ws, wsb = _ws_args(int(G) * _lib.lib().mvae_gemm_ws_bytes(M, N, K), x.device)
+    check(_lib.lib().mvae_linear_fwd_grouped(_ptr(x), x.stride(0), 0, _ptr(w0), w_gs, _ptr(b0), b_gs, _ptr(pre), _ptr(act),
+                                             out.stride(1), out.stride(0), int(G), M, N, K, ws, wsb, _stream()),
+          'mvae_linear_fwd_grouped')
+
+
 def linear_dgrad_grouped(dy, w0, w_gs, dx, pre_in=None, accumulate=False):
     _need_gpu(dy, w0, dx, pre_in)
     G, M, N = _g3(dy, 'dy').shape
@@ -1348,6 +1367,66 @@ def iw_score_multi(lw, segs, state, out=None, finish_k=0):
     ws, ws_bytes = _ws_args(nbytes, lw.device)
     check(_lib.lib().mvae_iw_score_multi(arr, len(segs), _ptr(lw), _ptr(state), _ptr(out), Kc, B, int(finish_k), ws,
                                          ws_bytes, _stream()), 'mvae_iw_score_multi')
+
+
+# ---------------------------------------------------------------------------- many one-logit modalities (K25)
+def heads_bce_rows(h, w0, w_gs, b0, b_gs, target, rec, logits_out=None, target_rows=None):
+    """The last layer of G one-logit heads fused with its Bernoulli term (mvae_heads_bce_rows): ``rec[g, r] =
+    bce(h[g, r] . w_g + bias_g, target[r % target_rows, g])``.  ``h`` [G, R, H] with unit column stride (the post-Swish
+    output of the third grouped Linear); ``w0`` / ``b0``: the weight row (H values) and the bias of group 0, ``w_gs`` /
+    ``b_gs`` the strides in floats to the next group's; ``target`` float {0, 1} [>= target_rows, >= G] with unit column
+    stride (a column range of a wider matrix qualifies), by default all its rows; ``rec`` and the optional ``logits_out``
+    [G, R] with unit column stride."""
+    _need_gpu(h, w0, b0, target, rec, logits_out)
+    G, R, H = _g3(h, 'h').shape
+    for t, name in ((h, 'h'), (w0, 'w0'), (b0, 'b0'), (target, 'target'), (rec, 'rec'), (logits_out, 'logits_out')):
+        if t is not None and t.dtype != torch.float32:
+            raise RuntimeError('heads_bce_rows: %s must be float32, got %s' % (name, t.dtype))
+    if w0.numel() != H or not w0.is_contiguous() or b0.numel() != 1:
+        raise RuntimeError('heads_bce_rows: w0 holds the %d weights and b0 the bias of group 0; got %s and %s'
+                           % (H, tuple(w0.shape), tuple(b0.shape)))
+    if target_rows is None:
+        target_rows = target.shape[0] if target.dim() == 2 else 0
+    if target.dim() != 2 or target.shape[1] < G or (target.shape[1] > 1 and target.stride(1) != 1) \
+            or not 1 <= int(target_rows) <= target.shape[0]:
+        raise RuntimeError('heads_bce_rows: target must be [>= target_rows, >= %d] with unit column stride, got %s'
+                           % (G, tuple(target.shape)))
+    ldt = target.stride(0) if target.shape[0] > 1 else max(G, target.stride(0))
+    for t, name in ((rec, 'rec'), (logits_out, 'logits_out')):
+        if t is not None and (t.dim() != 2 or tuple(t.shape) != (G, R) or (R > 1 and t.stride(1) != 1)
+                              or (G > 1 and t.stride(0) < R)):
+            raise RuntimeError('heads_bce_rows: %s must be [%d, %d] with unit column stride' % (name, G, R))
+    check(_lib.lib().mvae_heads_bce_rows(_ptr(h), h.stride(1), h.stride(0), _ptr(w0), int(w_gs), _ptr(b0), int(b_gs),
+                                         _ptr(target), int(target_rows), int(ldt), _ptr(rec), rec.stride(0),
+                                         _ptr(logits_out), logits_out.stride(0) if logits_out is not None else 0,
+                                         G, R, H, _stream()), 'mvae_heads_bce_rows')
+
+
+def iw_fold_rows(lw, rec, sel, state, out=None, finish_k=0):
+    """The chunk ``lw[Kc, B]`` and the existing loss rows ``rec`` [rows, >= Kc * B] (unit column stride; -log p in
+    ``lw``'s sample-major order) folded into ``state[S + 1, B, 2]`` (mvae_iw_fold_rows, K25): state j takes ``lw -
+    rec[sel[j]]``, state S takes ``lw - (rec[sel[0]] + ... + rec[sel[S-1]])`` (the joint).  ``sel``: up to
+    ``_lib.IW_FOLD_MAX`` row indices of ``rec`` (host ints), None for all rows in order.  Start every state at (-inf, 0);
+    ``finish_k`` as in ``iw_accumulate``, with ``out`` [S + 1, B]."""
+    _need_gpu(lw, rec, state, out); _f32c(lw, state, out)
+    if rec.dtype != torch.float32 or rec.dim() != 2 or (rec.shape[1] > 1 and rec.stride(1) != 1):
+        raise RuntimeError('iw_fold_rows: rec must be float32 [rows, >= Kc * B] with unit column stride')
+    sel = list(range(rec.shape[0])) if sel is None else [int(s) for s in sel]
+    S = len(sel)
+    if not 1 <= S <= _lib.IW_FOLD_MAX or any(not 0 <= s < rec.shape[0] for s in sel):
+        raise RuntimeError('iw_fold_rows: sel must name 1 to %d of the %d rows of rec, got %s'
+                           % (_lib.IW_FOLD_MAX, rec.shape[0], sel))
+    if lw.dim() != 2 or tuple(state.shape) != (S + 1, lw.shape[1], 2):
+        raise RuntimeError('iw_fold_rows: lw [Kc, B] and state [S + 1, B, 2] for S rows; got %s and %s for %d'
+                           % (tuple(lw.shape), tuple(state.shape), S))
+    Kc, B = lw.shape
+    if rec.shape[1] < Kc * B:
+        raise RuntimeError('iw_fold_rows: a row of rec holds %d values for %d x %d samples' % (rec.shape[1], Kc, B))
+    rec_ss = rec.stride(0) if rec.shape[0] > 1 else max(Kc * B, rec.stride(0))
+    if finish_k and (out is None or tuple(out.shape) != (S + 1, B)):
+        raise RuntimeError('iw_fold_rows: finish needs out [S + 1, B]')
+    check(_lib.lib().mvae_iw_fold_rows(_ptr(rec), rec_ss, (ctypes.c_int * S)(*sel), S, _ptr(lw), _ptr(state), _ptr(out),
+                                       Kc, B, int(finish_k), _stream()), 'mvae_iw_fold_rows')
 
 
 # ---------------------------------------------------------------------------- MultiMNIST dataset builder

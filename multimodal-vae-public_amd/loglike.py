@@ -18,7 +18,8 @@ MultiMNIST's text term minus the four positions' cross-entropy rows.  The README
 
 Everything stays on the device: per chunk of ``Kc`` samples one ``mvae_iw_draw`` launch (draw + density ratio), the
 scored decoders on the ``Kc * B`` sample-major rows, the existing loss-row kernels, and one ``mvae_iw_accumulate``
-launch (streaming log-mean-exp).  ``celeba19`` (19 modalities) is out of scope."""
+launch (streaming log-mean-exp).  ``celeba19`` (19 modalities) is refused here: its estimator is
+``celeba19/loglike.py`` (19 marginals and the joint from one pass)."""
 import torch
 
 from . import kernels as K
