@@ -398,6 +398,30 @@ int mvae_bn_train_bwd(const float *dy, const float *x, const float *gamma, const
                       float *dx, float *dgamma, float *dbeta,
                       int G, int B, int C, int HW, int flags,
                       void *ws, size_t ws_bytes, mvae_stream_t stream);
+/* Which kernel mvae_bn_train_fwd (bwd = 0) / mvae_bn_train_bwd (bwd != 0) takes for a shape -- the route function the
+ * launches themselves switch on (csrc/norm.hip bn_shape + bn_route).  Host only: launches nothing, allocates nothing,
+ * touches no device, holds no state.
+ *   aligned    x, y / dy and dx are all 16-byte aligned (an operand that is not takes every HW onto the scalar kernels)
+ *   slices     (may be NULL) S, the batch slices per (group, channel) of the two-launch routes; 1 for the others
+ *   launches   (may be NULL) kernel launches of the call: 2 for the two-launch routes, 1 for the fused and BatchNorm1d
+ *              routes; MVAE_BNROUTE_SLICE reports 2, the call WITH running statistics (its second launch advances them and
+ *              is skipped when running_mean == NULL)
+ *   returns    a MVAE_BNROUTE_* code, or the MVAE_ERR_ARG the launch would return for this shape (a non-positive
+ *              dimension, B * HW >= 2^31, G * B * C * HW >= 2^40).  Null pointers and the workspace size (MVAE_ERR_WS) are
+ *              the launch's own checks and not repeated here. */
+#define MVAE_BNROUTE_TWO_VEC_ROWS     1   /* bn_partial_stats / bn_fwd_apply / bn_bwd_partial / bn_bwd_apply, float4 sweep, a row per HW/4 lanes */
+#define MVAE_BNROUTE_TWO_VEC_COLS     2   /* ... float4 sweep, lanes walk the columns of a row (HW/4 no power of two, or HW > 1024) */
+#define MVAE_BNROUTE_TWO_SCALAR       3   /* ... one element per lane (HW % 4 != 0, or an unaligned operand) */
+#define MVAE_BNROUTE_FUSED_VEC_G1     4   /* bn_fused_{fwd,bwd}_kernel<true, 1, 4>: all groups in one block, float4 units */
+#define MVAE_BNROUTE_FUSED_VEC_G2     5   /* <true, 2, 4> */
+#define MVAE_BNROUTE_FUSED_VEC_G3     6   /* <true, 3, 4>: forward only */
+#define MVAE_BNROUTE_FUSED_SCALAR_G1  7   /* <false, 1, 16>: 16 one-element units per thread */
+#define MVAE_BNROUTE_FUSED_SCALAR_GN  8   /* <false, 3 (forward) / 2 (backward), 8>: 8 units per thread and group */
+#define MVAE_BNROUTE_BN1D_G1          9   /* bn1d_fused_{fwd,bwd}_kernel<1>: HW = 1, 16 columns per block */
+#define MVAE_BNROUTE_BN1D_GN         10   /* bn1d_fused_{fwd,bwd}_kernel<3> */
+#define MVAE_BNROUTE_SLICE           11   /* bn_slice_fwd_kernel (+ bn_running_kernel): forward only */
+int mvae_bn_route(int bwd, int G, int B, int C, int HW, int aligned, int *slices /* may be NULL */,
+                  int *launches /* may be NULL */);
 /* saved + running statistics of G groups from the records of mvae_convT2d_k4_fwd_stats (`tiles` records of
  * `elems_per_tile` elements per channel; tiles % G == 0, a group's tiles contiguous).  save_* may be NULL. */
 int mvae_bn_stats_merge(const float *part, int tiles, int elems_per_tile, int G, int C,

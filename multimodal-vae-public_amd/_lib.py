@@ -48,6 +48,10 @@ LINEAR_ROUTES = {1: 'gemm2', 2: 'g2s_32x64_k4', 3: 'g2s_64x32_k4', 4: 'g2s_32x64
                  42: 'wgrad_direct_8', 43: 'wgrad_direct_16', 50: 'wgrad_batched2', 51: 'wgrad_batched',
                  52: 'wgrad_batched_adam'}
 
+# mvae_bn_route: the kernels the training-mode BatchNorm launches choose between (MVAE_BNROUTE_*)
+BN_ROUTES = {1: 'two_vec_rows', 2: 'two_vec_cols', 3: 'two_scalar', 4: 'fused_vec_g1', 5: 'fused_vec_g2',
+             6: 'fused_vec_g3', 7: 'fused_scalar_g1', 8: 'fused_scalar_gn', 9: 'bn1d_g1', 10: 'bn1d_gn', 11: 'slice'}
+
 
 class Experts(ctypes.Structure):
     _fields_ = [('mu', c_void_p * MAX_EXPERTS), ('logvar', c_void_p * MAX_EXPERTS)]
@@ -120,6 +124,7 @@ _SIGNATURES = {
     'mvae_bn_train_fwd': (c_int, [P] * 8 + [c_int] * 4 + [c_float, c_float, c_int, P, c_int, P, c_size_t, P]),
     'mvae_bn_train_bwd': (c_int, [P] * 9 + [c_int] * 5 + [P, c_size_t, P]),
     'mvae_bn_eval_fwd': (c_int, [P] * 6 + [c_int] * 3 + [c_float, c_int, P]),
+    'mvae_bn_route': (c_int, [c_int] * 6 + [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     'mvae_swish_fwd': (c_int, [P, P, c_size_t, P]),
     'mvae_swish_bwd': (c_int, [P, P, P, c_size_t, P]),
     'mvae_sigmoid_fwd': (c_int, [P, P, c_size_t, P]),

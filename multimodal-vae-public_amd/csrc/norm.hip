@@ -22,7 +22,14 @@ struct BnShape {
     int rows, vec, tx;          // vec: HW % 4 == 0 (float4 path); tx = threads along a row (power of two)
 };
 
-__host__ __device__ inline int bn_max_slices(int n_per_group) { return n_per_group / BN_SLICE_ELEMS + 2; }
+// an upper bound of S from n = B * HW alone (mvae_bn_ws_bytes sees nothing else).  A slice is rows = floor(8192 / HW) batch
+// rows, and the floor loses up to half a slice: rows >= 8192 / (2 HW), so S = ceil(B / rows) <= n / 4096 + 1; with
+// HW > 8192 a slice is one row and S = B < n / 8192.  (n / 8192 + 2 refused 56x56 maps at B = 32: S = 16 against 14.)
+__host__ __device__ inline int bn_max_slices(int n_per_group) { return n_per_group / (BN_SLICE_ELEMS / 2) + 2; }
+
+// the float4 sweep of a slice: lanes take the float4 columns of a row and rows run in parallel (true: a row fits the tx
+// lanes), or the block's row classes walk the columns of their rows (false: HW / 4 is no power of two, or HW > 1024)
+__host__ __device__ inline bool bn_vec_rows(const BnShape &sh) { return (sh.HW >> 2) <= sh.tx; }
 
 // f4(offset) is called with the element offset of each aligned float4 of the slice (vec path),
 // f1(offset) with each scalar element (HW not a multiple of 4, e.g. 5x5 maps and BatchNorm1d).
@@ -33,7 +40,7 @@ __device__ __forceinline__ void bn_slice_loop(const BnShape &sh, int g, int c, i
         const int hw4 = sh.HW >> 2, tx = threadIdx.x & (sh.tx - 1), ty = threadIdx.x / sh.tx;
         const int ny = BN_THREADS / sh.tx;
         // four rows (or four float4 columns) per trip: independent loads in flight instead of one per iteration
-        if (hw4 <= sh.tx) {
+        if (bn_vec_rows(sh)) {
             const bool col_ok = tx < hw4;
             const size_t row_stride = (size_t)sh.C * sh.HW;
             int b = b_lo + ty;
@@ -791,7 +798,7 @@ inline int bn_fused_kind(const BnShape &sh, bool bwd) {
             sh.G <= 65535 && (sh.HW >> 2) <= BNF_THREADS && BNF_THREADS % (sh.HW >> 2) == 0) ? 3 : 0;
 }
 
-inline bool bn_shape(int G, int B, int C, int HW, const void *a, const void *b, const void *c, BnShape *sh) {
+inline bool bn_shape(int G, int B, int C, int HW, bool aligned, BnShape *sh) {
     if (G <= 0 || B <= 0 || C <= 0 || HW <= 0) return false;
     if ((long)G * B * C * HW >= (1L << 40) || (long)B * HW >= (1L << 31)) return false;
     sh->G = G; sh->B = B; sh->C = C; sh->HW = HW; sh->n = B * HW;
@@ -799,11 +806,31 @@ inline bool bn_shape(int G, int B, int C, int HW, const void *a, const void *b, 
     if (sh->rows < 1) sh->rows = 1;
     if (sh->rows > B) sh->rows = B;
     sh->S = (B + sh->rows - 1) / sh->rows;
-    sh->vec = (HW % 4 == 0) && aligned16(a) && (!b || aligned16(b)) && (!c || aligned16(c));
+    sh->vec = (HW % 4 == 0) && aligned;
     int tx = 1;
     while (tx * 2 <= (HW >> 2) && tx * 2 <= BN_THREADS) tx *= 2;
     sh->tx = tx;
     return sh->S <= bn_max_slices(sh->n);
+}
+inline bool bn_aligned(const void *a, const void *b, const void *c) {
+    return aligned16(a) && (!b || aligned16(b)) && (!c || aligned16(c));
+}
+
+// The kernel a training launch takes (MVAE_BNROUTE_*): mvae_bn_train_fwd / _bwd switch on it, mvae_bn_route reports it --
+// the decision exists once.
+inline int bn_route(const BnShape &sh, bool bwd) {
+    switch (bn_fused_kind(sh, bwd)) {
+        case 3: return MVAE_BNROUTE_SLICE;
+        case 2: return sh.G == 1 ? MVAE_BNROUTE_BN1D_G1 : MVAE_BNROUTE_BN1D_GN;
+        case 1:
+            if (!sh.vec) return sh.G == 1 ? MVAE_BNROUTE_FUSED_SCALAR_G1 : MVAE_BNROUTE_FUSED_SCALAR_GN;
+            return sh.G == 1 ? MVAE_BNROUTE_FUSED_VEC_G1 : sh.G == 2 ? MVAE_BNROUTE_FUSED_VEC_G2 : MVAE_BNROUTE_FUSED_VEC_G3;
+        default: break;
+    }
+    return !sh.vec ? MVAE_BNROUTE_TWO_SCALAR : bn_vec_rows(sh) ? MVAE_BNROUTE_TWO_VEC_ROWS : MVAE_BNROUTE_TWO_VEC_COLS;
+}
+inline bool bn_route_two_launch(int route) {
+    return route == MVAE_BNROUTE_TWO_VEC_ROWS || route == MVAE_BNROUTE_TWO_VEC_COLS || route == MVAE_BNROUTE_TWO_SCALAR;
 }
 
 }  // namespace
@@ -813,18 +840,30 @@ MVAE_EXPORT size_t mvae_bn_ws_bytes(int G, int C, int n_per_group) {
     return (size_t)G * C * bn_max_slices(n_per_group) * 3 * sizeof(float);
 }
 
+// which launch a call would take: bn_shape + bn_route, the functions the launches themselves go through.  Pure host code.
+MVAE_EXPORT int mvae_bn_route(int bwd, int G, int B, int C, int HW, int aligned, int *slices, int *launches) {
+    BnShape sh;
+    if (!bn_shape(G, B, C, HW, aligned != 0, &sh)) return MVAE_ERR_ARG;
+    const int route = bn_route(sh, bwd != 0);
+    const bool two = bn_route_two_launch(route);
+    if (slices) *slices = two ? sh.S : 1;
+    if (launches) *launches = (two || route == MVAE_BNROUTE_SLICE) ? 2 : 1;
+    return route;
+}
+
 MVAE_EXPORT int mvae_bn_train_fwd(const float *x, const float *gamma, const float *beta, float *y,
                                   float *save_mean, float *save_invstd, float *running_mean,
                                   float *running_var, int G, int B, int C, int HW, float eps, float momentum,
                                   int n_updates, const int *n_updates_dev, int flags, void *ws,
                                   size_t ws_bytes, mvae_stream_t stream) {
     BnShape sh;
-    if (!x || !gamma || !beta || !save_mean || !save_invstd || !bn_shape(G, B, C, HW, x, y, nullptr, &sh))
+    if (!x || !gamma || !beta || !save_mean || !save_invstd || !bn_shape(G, B, C, HW, bn_aligned(x, y, nullptr), &sh))
         return MVAE_ERR_ARG;
     if ((running_mean == nullptr) != (running_var == nullptr)) return MVAE_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int sw = (flags & MVAE_ACT_SWISH) ? 1 : 0;
-    if (bn_fused_kind(sh, false) == 3) {
+    const int route = bn_route(sh, false);
+    if (route == MVAE_BNROUTE_SLICE) {
         if (!ws || ws_bytes < (size_t)G * C * 2 * sizeof(float)) return MVAE_ERR_WS;
         hipLaunchKernelGGL(bn_slice_fwd_kernel, dim3(C, G), dim3(BNF_THREADS), 0, st, x, gamma, beta, y, save_mean,
                            save_invstd, (float *)ws, sh, eps, sw);
@@ -833,20 +872,19 @@ MVAE_EXPORT int mvae_bn_train_fwd(const float *x, const float *gamma, const floa
                                running_mean, running_var, momentum, n_updates, n_updates_dev);
         return mvae_launch_status();
     }
-    if (const int kind = bn_fused_kind(sh, false)) {
+    if (!bn_route_two_launch(route)) {
 #define MVAE_BNF_FWD(KERN, GRID)                                                                                    \
         hipLaunchKernelGGL(KERN, dim3(GRID), dim3(BNF_THREADS), 0, st, x, gamma, beta, y, save_mean, save_invstd,   \
                            running_mean, running_var, sh, eps, momentum, n_updates, n_updates_dev, sw)
-        if (kind == 2) {
-            if (G == 1) MVAE_BNF_FWD((bn1d_fused_fwd_kernel<1>), (C + BN1_COLS - 1) / BN1_COLS);
-            else MVAE_BNF_FWD((bn1d_fused_fwd_kernel<BN1_GMAX>), (C + BN1_COLS - 1) / BN1_COLS);
-        } else if (sh.vec) {
-            if (G == 1) MVAE_BNF_FWD((bn_fused_fwd_kernel<true, 1, 4>), C);
-            else if (G == 2) MVAE_BNF_FWD((bn_fused_fwd_kernel<true, 2, 4>), C);
-            else MVAE_BNF_FWD((bn_fused_fwd_kernel<true, BNF_GMAX_FWD, 4>), C);
-        } else {
-            if (G == 1) MVAE_BNF_FWD((bn_fused_fwd_kernel<false, 1, 16>), C);
-            else MVAE_BNF_FWD((bn_fused_fwd_kernel<false, BNF_GMAX_FWD, 8>), C);
+        switch (route) {
+            case MVAE_BNROUTE_BN1D_G1: MVAE_BNF_FWD((bn1d_fused_fwd_kernel<1>), (C + BN1_COLS - 1) / BN1_COLS); break;
+            case MVAE_BNROUTE_BN1D_GN: MVAE_BNF_FWD((bn1d_fused_fwd_kernel<BN1_GMAX>), (C + BN1_COLS - 1) / BN1_COLS); break;
+            case MVAE_BNROUTE_FUSED_VEC_G1: MVAE_BNF_FWD((bn_fused_fwd_kernel<true, 1, 4>), C); break;
+            case MVAE_BNROUTE_FUSED_VEC_G2: MVAE_BNF_FWD((bn_fused_fwd_kernel<true, 2, 4>), C); break;
+            case MVAE_BNROUTE_FUSED_VEC_G3: MVAE_BNF_FWD((bn_fused_fwd_kernel<true, BNF_GMAX_FWD, 4>), C); break;
+            case MVAE_BNROUTE_FUSED_SCALAR_G1: MVAE_BNF_FWD((bn_fused_fwd_kernel<false, 1, 16>), C); break;
+            case MVAE_BNROUTE_FUSED_SCALAR_GN: MVAE_BNF_FWD((bn_fused_fwd_kernel<false, BNF_GMAX_FWD, 8>), C); break;
+            default: return MVAE_ERR_ARG;
         }
 #undef MVAE_BNF_FWD
         return mvae_launch_status();
@@ -879,24 +917,24 @@ MVAE_EXPORT int mvae_bn_train_bwd(const float *dy, const float *x, const float *
                                   size_t ws_bytes, mvae_stream_t stream) {
     BnShape sh;
     if (!dy || !x || !gamma || !beta || !save_mean || !save_invstd || !dx || !dgamma || !dbeta ||
-        !bn_shape(G, B, C, HW, x, dy, dx, &sh))
+        !bn_shape(G, B, C, HW, bn_aligned(x, dy, dx), &sh))
         return MVAE_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int swish = (flags & MVAE_ACT_SWISH) ? 1 : 0;
-    if (const int kind = bn_fused_kind(sh, true)) {
+    const int route = bn_route(sh, true);
+    if (!bn_route_two_launch(route)) {
         const int acc = (flags & MVAE_ACCUMULATE) ? 1 : 0;
 #define MVAE_BNF_BWD(KERN, GRID)                                                                                    \
         hipLaunchKernelGGL(KERN, dim3(GRID), dim3(BNF_THREADS), 0, st, dy, x, gamma, beta, save_mean, save_invstd,  \
                            dx, dgamma, dbeta, sh, swish, acc)
-        if (kind == 2) {
-            if (G == 1) MVAE_BNF_BWD((bn1d_fused_bwd_kernel<1>), (C + BN1_COLS - 1) / BN1_COLS);
-            else MVAE_BNF_BWD((bn1d_fused_bwd_kernel<BN1_GMAX>), (C + BN1_COLS - 1) / BN1_COLS);
-        } else if (sh.vec) {
-            if (G == 1) MVAE_BNF_BWD((bn_fused_bwd_kernel<true, 1, 4>), C);
-            else MVAE_BNF_BWD((bn_fused_bwd_kernel<true, BNF_GMAX_BWD, 4>), C);
-        } else {
-            if (G == 1) MVAE_BNF_BWD((bn_fused_bwd_kernel<false, 1, 16>), C);
-            else MVAE_BNF_BWD((bn_fused_bwd_kernel<false, BNF_GMAX_BWD, 8>), C);
+        switch (route) {
+            case MVAE_BNROUTE_BN1D_G1: MVAE_BNF_BWD((bn1d_fused_bwd_kernel<1>), (C + BN1_COLS - 1) / BN1_COLS); break;
+            case MVAE_BNROUTE_BN1D_GN: MVAE_BNF_BWD((bn1d_fused_bwd_kernel<BN1_GMAX>), (C + BN1_COLS - 1) / BN1_COLS); break;
+            case MVAE_BNROUTE_FUSED_VEC_G1: MVAE_BNF_BWD((bn_fused_bwd_kernel<true, 1, 4>), C); break;
+            case MVAE_BNROUTE_FUSED_VEC_G2: MVAE_BNF_BWD((bn_fused_bwd_kernel<true, BNF_GMAX_BWD, 4>), C); break;
+            case MVAE_BNROUTE_FUSED_SCALAR_G1: MVAE_BNF_BWD((bn_fused_bwd_kernel<false, 1, 16>), C); break;
+            case MVAE_BNROUTE_FUSED_SCALAR_GN: MVAE_BNF_BWD((bn_fused_bwd_kernel<false, BNF_GMAX_BWD, 8>), C); break;
+            default: return MVAE_ERR_ARG;    // FUSED_VEC_G3 and SLICE are forward forms: bn_route(.., true) never returns them
         }
 #undef MVAE_BNF_BWD
         return mvae_launch_status();

@@ -609,6 +609,19 @@ def bn_train_bwd(dy, x, gamma, beta, save_mean, save_invstd, dx, dgamma, dbeta, 
                                        G, B, C, HW, flags, ws, wsb, _stream()), 'mvae_bn_train_bwd')
 
 
+def bn_route(G, B, C, HW, bwd=False, aligned=True):
+    """(route, slices, launches) of ``bn_train_fwd`` (``bwd=True``: ``bn_train_bwd``) on G groups of B rows, C channels
+    and HW spatial positions (1: BatchNorm1d) -- the name of the kernel it takes (``_lib.BN_ROUTES``), the batch slices S
+    per (group, channel) of the two-launch routes (1 for the others) and the number of kernel launches ('slice': 2, the
+    call with running statistics).  ``aligned``: x, y / dy and dx are all 16-byte aligned.  Host only (mvae_bn_route: the
+    route function the launch itself switches on).  Raises where the launch would refuse the shape."""
+    sl, ln = ctypes.c_int(0), ctypes.c_int(0)
+    rc = _lib.lib().mvae_bn_route(1 if bwd else 0, G, B, C, HW, 1 if aligned else 0, ctypes.byref(sl), ctypes.byref(ln))
+    if rc <= 0:
+        check(rc if rc < 0 else -1, 'mvae_bn_route')
+    return _lib.BN_ROUTES[rc], sl.value, ln.value
+
+
 def bn_eval_fwd(x, gamma, beta, y, running_mean, running_var, eps=1e-5, swish=True):
     _need_gpu(x, gamma, beta, y, running_mean, running_var)
     _f32c(x, gamma, beta, y, running_mean, running_var)
