@@ -1000,6 +1000,47 @@ int mvae_iw_fold_rows(const float *rec, size_t rec_ss, const int *sel /* host, n
                       float *state, float *out /* nullable */, int Kc, int B, int finish_k, mvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * K26  Canny edge detection for a batch of uint8 images in HBM (csrc/vision_setup.hip): the edge step of the reference's
+ *      vision/setup.py:55-75, which calls scikit-image's feature.canny(image / 255., sigma) per file.  What is computed is
+ *      that function's documented algorithm on a float image in [0, 1] with its default thresholds and no mask:
+ *   1 luma      g = u8 / 255; with channels == 3 first L = (R * 19595 + G * 38470 + B * 7471 + 0x8000) >> 16 (Pillow's
+ *               convert('L'), the luma of K23).
+ *   2 blur      taps w[k] = exp(-k^2 / 2 sigma^2), |k| <= r = int(4 sigma + 0.5), normalised to sum 1 (built on the host
+ *               in double, used as fp32); separable, down the columns then along the rows, zeros outside the image; divided by the same blur
+ *               of an all-ones image, by[y] * bx[x].
+ *   3 gradient  isobel along rows, jsobel along columns: the unnormalised 3 x 3 Sobel (1-2-1 across, -1 0 +1 along) of the
+ *               blurred image with its border sample duplicated; mag = sqrt(isobel^2 + jsobel^2).
+ *   4 maxima    candidates: pixels not on the image border with mag > 0.  With ai = |isobel|, aj = |jsobel| and
+ *               (c1, c2, w) =   same sign (both >= 0 or both <= 0), ai >= aj:  (+1, 0)  (+1, +1)  aj / ai
+ *                               same sign, ai <= aj:                           (0, +1)  (+1, +1)  ai / aj
+ *                               opposite sign, ai <= aj:                       (0, +1)  (-1, +1)  ai / aj
+ *                               opposite sign, ai >= aj:                       (-1, 0)  (-1, +1)  aj / ai
+ *               ((dy, dx) offsets; the cases are applied in this order, a later one overwrites an earlier one), a
+ *               candidate is a local maximum when mag[c2] * w + mag[c1] * (1 - w) <= mag with these offsets and with
+ *               them negated.
+ *   5 classes   2 (strong): a local maximum with mag >= high; 1 (weak): one with low <= mag < high; 0: the rest.
+ *   6 edges     255 where the 8-connected component of non-zero classes a pixel lies in holds a strong pixel, else 0.
+ *   src [B, H, W] (channels 1) or [B, H, W, 3] (channels 3), edges / cls [B, H, W] uint8, mag [B, H, W] float; cls and mag
+ *   may be NULL.  The uint8 pointers may have any byte alignment (mag: a float's).  Two launches: a tiled float stage
+ *   (32 x 32 pixels per block, steps 1-5, one class byte per pixel into cls or, when cls is NULL, into ws) and the
+ *   hysteresis (one block per image, the class plane in LDS).  mvae_canny_hysteresis is step 6 alone on a caller's class
+ *   plane (a value above 2 counts as strong).  No atomics: the same inputs give the same bits.
+ *   mvae_canny_supported: 1 when H, W >= 3, 0 < sigma and r <= 16 (sigma < 4.125), and (H + 2) * ((W + 11) & ~3) <= 144 KiB
+ *   (the padded class plane of one image in one block's LDS; 218 x 178 is 41.4 KB); else 0.  Host-only.
+ *   mvae_canny_ws_bytes: B * H * W, or 0 for a shape the launch refuses.  Host-only.  ws is not read when cls is given.
+ *   Refused on the host before any launch: a null src / edges (mvae_canny_hysteresis: cls / edges), channels other than
+ *   1 or 3, B <= 0, a shape or sigma mvae_canny_supported refuses, low < 0, high < low, a NaN or infinite threshold --
+ *   MVAE_ERR_ARG; cls NULL and ws NULL or smaller than mvae_canny_ws_bytes -- MVAE_ERR_WS.
+ * ------------------------------------------------------------------------------------ */
+int mvae_canny_supported(int H, int W, float sigma);
+size_t mvae_canny_ws_bytes(int B, int H, int W);
+int mvae_canny(const uint8_t *src, int channels /* 1: gray [B,H,W]; 3: RGB [B,H,W,3] */, int B, int H, int W,
+               float sigma, float low, float high,
+               uint8_t *edges /* [B,H,W], 0 or 255 */, uint8_t *cls /* nullable [B,H,W]: 0 none, 1 weak, 2 strong */,
+               float *mag /* nullable [B,H,W] */, void *ws, size_t ws_bytes, mvae_stream_t stream);
+int mvae_canny_hysteresis(const uint8_t *cls, uint8_t *edges, int B, int H, int W, mvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * C1  Gradient exchange of data-parallel replicas -- RCCL over xGMI.
  *     The reference has NO counterpart: it is single-process, single-device (no DataParallel, no
  *     torch.distributed anywhere; README.md:47 `CUDA_VISIBLE_DEVICES=0`).  What this replaces is what N

@@ -234,6 +234,11 @@ _SIGNATURES = {
     'mvae_heads_bce_rows': (c_int, [P, c_int, c_size_t, P, c_size_t, P, c_size_t, P, c_int, c_int, P, c_size_t, P,
                                     c_size_t, c_int, c_int, c_int, P]),
     'mvae_iw_fold_rows': (c_int, [P, c_size_t, ctypes.POINTER(c_int), c_int, P, P, P, c_int, c_int, c_int, P]),
+    # K26: Canny edges of a uint8 batch (float stage + hysteresis), the edge step of vision/setup.py
+    'mvae_canny_supported': (c_int, [c_int, c_int, c_float]),
+    'mvae_canny_ws_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'mvae_canny': (c_int, [P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, P, P, P, P, c_size_t, P]),
+    'mvae_canny_hysteresis': (c_int, [P, P, c_int, c_int, c_int, P]),
     # C1: the gradient exchange (RCCL bound at run time)
     'mvae_comm_use_library': (c_int, [ctypes.c_char_p]),
     'mvae_comm_rccl_version': (c_int, []),

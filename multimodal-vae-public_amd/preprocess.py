@@ -4,6 +4,7 @@
     Compose([Resize(64), CenterCrop(64), ToTensor()])
                                   (celeba/train.py:146-148)       -> ``ResizeCenterCropToTensor(64)(u8_nhwc)``
     the six modalities of one item  (vision/datasets.py:54-91)    -> ``VisionCompose(64)(rgb, edge, mask, mark, gray)``
+    feature.canny(image / 255., sigma=2)  (vision/setup.py:70-73) -> ``Canny(2.0)(u8)``
 
 Input: raw ``uint8`` images already in HBM (``[B, H, W]`` / ``[B, H, W, 3]``, the decoded JPEG / IDX
 bytes); output: the ``float32`` NCHW batch the MVAE step consumes.  Resize is byte-exact with Pillow's
@@ -87,6 +88,79 @@ class ResizeCenterCropToTensor(object):
                                                     _ptr(bx), ksx, _ptr(ky), _ptr(by), ksy, y0, y1, _stream()),
               'mvae_resize_crop_u8_to_f32')
         return out
+
+
+class Canny(object):
+    """Canny edges of a uint8 batch on the device (csrc/vision_setup.hip): what the reference's ``vision/setup.py edge``
+    computes per file with ``skimage.feature.canny(image / 255., sigma=2)``.  ``__call__(u8)`` takes [B, H, W] (gray) or
+    [B, H, W, 3] (RGB: Pillow's ``convert('L')`` first) and returns the edge map [B, H, W] uint8, 0 or 255.
+
+    What is computed is scikit-image's DOCUMENTED algorithm (Gaussian blur normalised by the blur of ones, Sobel, bilinear
+    non-maximum suppression, thresholds ``low`` / ``high`` on the gradient magnitude, 8-connected hysteresis; spelled out
+    under K26 in include/mvae_hip.h and restated in tests/vision_setup_ref.py), not a particular release of that library:
+    newer releases differ in details such as ``>`` against ``>=`` at the thresholds.
+
+    The blur taps are built by the library per call (33 numbers at most, passed by value) and the normalisation is
+    rebuilt per tile on the device, so there is no table to cache: per (H, W) the op keeps the library's verdict on the
+    shape, per device one workspace (the class plane between the two launches) that grows to the largest batch seen."""
+
+    def __init__(self, sigma=2.0, low=0.1, high=0.2):
+        self.sigma, self.low, self.high = float(sigma), float(low), float(high)
+        if not (0.0 <= self.low <= self.high < float('inf')):
+            raise ValueError('Canny: need 0 <= low <= high, got low=%r high=%r' % (low, high))
+        self._shapes = {}
+        self._ws = {}
+
+    def _check(self, u8):
+        if not torch.is_tensor(u8) or u8.dtype != torch.uint8:
+            raise TypeError('Canny expects a uint8 tensor, got %s' % getattr(u8, 'dtype', type(u8)))
+        if u8.dim() not in (3, 4) or (u8.dim() == 4 and u8.shape[3] != 3) or u8.shape[0] <= 0:
+            raise ValueError('Canny expects a non-empty [B, H, W] or [B, H, W, 3] batch, got %s' % (tuple(u8.shape),))
+        B, H, W = (int(s) for s in u8.shape[:3])
+        if (H, W) not in self._shapes:
+            self._shapes[(H, W)] = bool(_lib.lib().mvae_canny_supported(H, W, self.sigma))
+        if not self._shapes[(H, W)]:
+            raise ValueError('Canny: images of %d x %d at sigma %g are not supported (needs H, W >= 3, a blur radius '
+                             'int(4 sigma + 0.5) <= 16 and a class plane that fits one block\'s LDS)' % (H, W, self.sigma))
+        _need_gpu(u8)
+        return B, H, W
+
+    def _run(self, u8, want_stages):
+        B, H, W = self._check(u8)
+        x = u8.contiguous()
+        edges = torch.empty(B, H, W, dtype=torch.uint8, device=x.device)
+        cls = mag = ws = None
+        need = 0
+        if want_stages:
+            cls = torch.empty(B, H, W, dtype=torch.uint8, device=x.device)
+            mag = torch.empty(B, H, W, dtype=torch.float32, device=x.device)
+        else:
+            need = _lib.lib().mvae_canny_ws_bytes(B, H, W)
+            ws = self._ws.get(x.device)
+            if ws is None or ws.numel() < need:
+                ws = self._ws[x.device] = torch.empty(need, dtype=torch.uint8, device=x.device)
+        check(_lib.lib().mvae_canny(_ptr(x), 3 if x.dim() == 4 else 1, B, H, W, self.sigma, self.low, self.high,
+                                    _ptr(edges), _ptr(cls), _ptr(mag), _ptr(ws), need, _stream()), 'mvae_canny')
+        return edges, cls, mag
+
+    def __call__(self, u8):
+        return self._run(u8, False)[0]
+
+    def stages(self, u8):
+        """(edges, cls, mag): the edge map, the class plane (0 none, 1 weak, 2 strong) and the gradient magnitude."""
+        return self._run(u8, True)
+
+
+def canny_hysteresis(cls):
+    """Step 6 of ``Canny`` alone: uint8 class planes [B, H, W] (0 none, 1 weak, >= 2 strong) -> edge maps, 0 or 255."""
+    if not torch.is_tensor(cls) or cls.dtype != torch.uint8 or cls.dim() != 3:
+        raise TypeError('canny_hysteresis expects a uint8 [B, H, W] tensor')
+    _need_gpu(cls)
+    x = cls.contiguous()
+    out = torch.empty_like(x)
+    check(_lib.lib().mvae_canny_hysteresis(_ptr(x), _ptr(out), x.shape[0], x.shape[1], x.shape[2], _stream()),
+          'mvae_canny_hysteresis')
+    return out
 
 
 class VisionCompose(object):

@@ -5,10 +5,11 @@
 the two further modalities and runs ``Resize(64) + CenterCrop(64) + ToTensor`` on all six, byte-exact with the per-item
 Pillow arithmetic of ``CelebVision``.
 
-Only Pillow is needed here.  The folders ``img_align_celeba_edge`` (Canny, scikit-image) and ``img_align_celeba_mask``
-(dlib landmarks) are written once by the reference's ``vision/setup.py``, which stays out of scope; whoever has run it has
-everything this module reads: ``Eval/list_eval_partition.txt``, ``img_align_celeba``, ``img_align_celeba_edge``,
-``img_align_celeba_mask`` and, optionally, ``img_align_celeba_grayscale``.
+Only Pillow is needed here.  The folder ``img_align_celeba_edge`` (Canny) is written once by ``vision/setup.py edge`` of
+this package (HIP kernels) or of the reference (scikit-image); ``img_align_celeba_mask`` (dlib landmarks) only by the
+reference's ``vision/setup.py``, whose mask builder stays out of scope.  This module reads
+``Eval/list_eval_partition.txt``, ``img_align_celeba``, ``img_align_celeba_edge``, ``img_align_celeba_mask`` and,
+optionally, ``img_align_celeba_grayscale``.
 
 Two defects of the reference text are repaired:
 
@@ -21,7 +22,15 @@ Two defects of the reference text are repaired:
 ``gray``: ``'folder'`` reads ``img_align_celeba_grayscale`` as the reference does, ``'rgb'`` takes Pillow's
 ``convert('L')`` of the colour image (on the device: the kernel's integer luma), ``'auto'`` is ``'folder'`` when the
 folder exists.  The grayscale folder holds JPEGs, so its pixels went through one more JPEG round trip than the luma of
-the colour file: ``'rgb'`` does not reproduce that round trip."""
+the colour file: ``'rgb'`` does not reproduce that round trip.
+
+``edge``: ``'folder'`` (the default, the reference's data) reads ``img_align_celeba_edge``; ``'canny'`` does not open that
+folder: the edge modality is ``preprocess.Canny`` (sigma 2, thresholds 0.1 / 0.2: what ``setup.py edge`` writes) of the
+colour image's luma, computed on the device -- by ``CelebVisionLoader`` on the uploaded colour batch, one more op in
+front of the compose launch, and by ``CelebVision.__getitem__`` on its one image (so the per-item surface needs a GPU
+in this mode and raises the usual "GPU" ``RuntimeError`` without one).  The same caveat as for ``gray='rgb'``: an edge
+folder of ``.jpg`` names went through a JPEG round trip after Canny, ``'canny'`` does not reproduce that round trip.  On
+a folder of lossless files the two modes give equal batches."""
 import os
 
 import numpy as np
@@ -36,11 +45,20 @@ IMAGE_DIR, GRAY_DIR, EDGE_DIR, MASK_DIR = ('img_align_celeba', 'img_align_celeba
                                            'img_align_celeba_mask')
 REQUIRED = (PARTITION_FILE, IMAGE_DIR, EDGE_DIR, MASK_DIR)
 GRAY_MODES = ('auto', 'folder', 'rgb')
+EDGE_MODES = ('folder', 'canny')
 
 
-def missing_data(data_dir):
-    """The entries of ``REQUIRED`` that are not under ``data_dir``."""
-    return [rel for rel in REQUIRED
+def check_edge_mode(edge):
+    if edge not in EDGE_MODES:
+        raise ValueError("edge must be one of %s, got %r" % (', '.join(EDGE_MODES), edge))
+    return edge
+
+
+def missing_data(data_dir, edge='folder'):
+    """The entries of ``REQUIRED`` that are not under ``data_dir``; with ``edge='canny'`` the edge folder is not needed."""
+    check_edge_mode(edge)
+    wanted = [rel for rel in REQUIRED if not (edge == 'canny' and rel == EDGE_DIR)]
+    return [rel for rel in wanted
             if not (os.path.isfile if rel == PARTITION_FILE else os.path.isdir)(os.path.join(data_dir, rel))]
 
 
@@ -106,31 +124,50 @@ class CelebVision(object):
     mask, obscured, watermark) of float tensors [C, size, size], computed on the host with Pillow.  The per-item yardstick:
     the train step does not go through it -- see ``CelebVisionLoader``."""
 
-    def __init__(self, partition='train', data_dir='./data', watermark_path='./watermark.png', gray='auto', size=64):
+    def __init__(self, partition='train', data_dir='./data', watermark_path='./watermark.png', gray='auto', size=64,
+                 edge='folder'):
         if partition not in VALID_PARTITIONS:
             raise AssertionError(partition)
         self.partition, self.data_dir, self.watermark_path = partition, data_dir, watermark_path
+        self.edge = check_edge_mode(edge)
+        self._canny = None
         self.gray_from_folder = gray_from_folder(gray, data_dir)
         self.image_paths = load_eval_partition(partition, data_dir=data_dir)
         self.size = int(len(self.image_paths))
         self.out_size = int(size)
 
     def load_sources(self, index):
-        """The decoded files of one item as PIL images: (rgb, edge, mask, gray or None)."""
+        """The decoded files of one item as PIL images: (rgb, edge, mask, gray or None); edge is None with
+        ``edge='canny'``."""
         from PIL import Image
         name = self.image_paths[index]
         rgb = Image.open(os.path.join(self.data_dir, IMAGE_DIR, name)).convert('RGB')
-        edge = Image.open(os.path.join(self.data_dir, EDGE_DIR, name)).convert('L')
+        edge = None
+        if self.edge == 'folder':
+            edge = Image.open(os.path.join(self.data_dir, EDGE_DIR, name)).convert('L')
         mask = Image.open(os.path.join(self.data_dir, MASK_DIR, name)).convert('L')
         gray = None
         if self.gray_from_folder:
             gray = Image.open(os.path.join(self.data_dir, GRAY_DIR, name)).convert('L')
         return rgb, edge, mask, gray
 
+    def canny_edges(self, image):
+        """``edge='canny'``: the edge map of one PIL colour image as a PIL 'L' image, by the device op on its luma."""
+        from PIL import Image
+        from ..preprocess import Canny
+        if self._canny is None:
+            self._canny = Canny()
+        u8 = torch.from_numpy(np.array(image.convert('L'), dtype=np.uint8))[None]
+        if torch.cuda.is_available():
+            u8 = u8.cuda()
+        return Image.fromarray(self._canny(u8)[0].cpu().numpy())
+
     def __getitem__(self, index):
         image, edge_image, mask_image, gray_image = self.load_sources(index)
         if gray_image is None:
             gray_image = image.convert('L')
+        if edge_image is None:
+            edge_image = self.canny_edges(image)
         obscured_image = obscure_image(image)
         watermark_image = add_watermark(image, watermark_path=self.watermark_path)
         image, gray_image, edge_image, mask_image, obscured_image, watermark_image = [
@@ -147,14 +184,16 @@ class CelebVision(object):
 class CelebVisionLoader(object):
     """The 6-tuple batches ``train_step`` / ``fused_step`` / ``test()`` take: the DataLoader over ``CelebVision`` of
     vision/train.py:138-144 with everything after the file decode on the GPU.  Per batch: Pillow decodes the three or
-    four files of every item (host threads), ONE pinned uint8 copy to HBM per source, ONE ``VisionCompose`` launch.  The
+    four files of every item (host threads), ONE pinned uint8 copy to HBM per source, ONE ``VisionCompose`` launch; with
+    ``edge='canny'`` the edge file is not opened and ``Canny`` runs on the uploaded colour batch before it.  The
     watermark is opened and resized once per image size and kept on the device.  All images of a batch must share a
     size (aligned CelebA: 218 x 178)."""
 
     def __init__(self, partition, data_dir, batch_size, shuffle, device, seed=0, watermark_path='./watermark.png',
-                 gray='auto', decode_threads=8, size=64):
-        from ..preprocess import VisionCompose
-        self.data = CelebVision(partition, data_dir, watermark_path=watermark_path, gray=gray, size=size)
+                 gray='auto', decode_threads=8, size=64, edge='folder'):
+        from ..preprocess import Canny, VisionCompose
+        self.data = CelebVision(partition, data_dir, watermark_path=watermark_path, gray=gray, size=size, edge=edge)
+        self._canny = Canny() if edge == 'canny' else None
         if not os.path.isfile(watermark_path):
             raise ValueError('the watermark file %s is missing' % watermark_path)
         self.batch_size, self.shuffle, self.device = int(batch_size), bool(shuffle), device
@@ -195,4 +234,6 @@ class CelebVisionLoader(object):
                 h, w = shapes.pop()
                 rgb, edge, mask, gray = [None if item0 is None else self._upload([item[s] for item in items])
                                          for s, item0 in enumerate(items[0])]
+                if self._canny is not None:
+                    edge = self._canny(rgb)
                 yield self._compose(rgb, edge, mask, self._mark(h, w), gray=gray)

@@ -213,6 +213,8 @@ def add_flags(parser):
                         help="the CelebA folders vision/train.py reads; its 'val' partition is evaluated [default: ./data]")
     parser.add_argument('--watermark-file', type=str, default='./watermark.png',
                         help='the image with an alpha channel pasted on for the watermark modality [default: ./watermark.png]')
+    from .train import add_edge_flag
+    add_edge_flag(parser)
     parser.add_argument('--chunk-rows', type=int, default=DEFAULT_CHUNK_ROWS,
                         help='decoder rows per chunk [default: %d]' % DEFAULT_CHUNK_ROWS)
     parser.add_argument('--seed', type=int, default=0)
@@ -230,7 +232,7 @@ def batches(args, device):
     from .datasets import CelebVisionLoader
     check_data(args)
     for batch in CelebVisionLoader('val', args.data_dir, args.batch_size, False, device,
-                                   watermark_path=args.watermark_file):
+                                   watermark_path=args.watermark_file, edge=args.edge):
         yield batch
 
 

@@ -23,9 +23,10 @@ selects one; ``fused`` is the default because it measured faster (9.9 against 28
 profiles/vision_step.txt).
 
 Without ``--synthetic`` the loaders are ``datasets.CelebVisionLoader`` over ``--data-dir`` ('train' shuffled, 'val' not;
-vision/train.py:138-144) with the watermark of ``--watermark-file``.  The edge and mask folders it reads are written by the
-reference's ``vision/setup.py`` (Canny edges, dlib face masks), which is out of scope here: when they are missing the script
-says so and exits."""
+vision/train.py:138-144) with the watermark of ``--watermark-file``.  The edge folder is written by ``vision/setup.py edge``
+(Canny on HIP kernels), or not needed at all with ``--edge canny`` (the loader derives the edges per batch on the GPU);
+the mask folder is written by the reference's ``vision/setup.py`` (dlib face masks), which is out of scope here.  When a
+folder is missing the script says so and exits."""
 import os
 import sys
 
@@ -190,17 +191,27 @@ def parser():
     p.add_argument('--watermark-file', type=str, default='./watermark.png',
                    help='the image with an alpha channel pasted onto the colour image for the watermark modality '
                         '[default: ./watermark.png]')
+    add_edge_flag(p)
     return p
+
+
+def add_edge_flag(p):
+    p.add_argument('--edge', choices=['folder', 'canny'], default='folder',
+                   help="'folder': read the edge folder vision/setup.py edge wrote; 'canny': derive the edge modality "
+                        "from the colour image on the GPU, no edge folder needed [default: folder]")
 
 
 def check_data(args):
     """Without --synthetic: exit with what is missing under --data-dir, or when --watermark-file is."""
     from .datasets import missing_data
-    missing = missing_data(args.data_dir)
+    missing = missing_data(args.data_dir, edge=args.edge)
     if missing:
-        raise SystemExit('the vision data set is not under --data-dir %s: missing %s.  Building the edge / mask folders '
-                         '(vision/setup.py: scikit-image Canny edges, dlib face masks) is out of scope here: run the '
-                         "reference's setup.py first, or run with --synthetic" % (args.data_dir, ', '.join(missing)))
+        raise SystemExit('the vision data set is not under --data-dir %s: missing %s.  The edge folder is written by '
+                         '`vision/setup.py edge in_dir out_dir` of this repository (Canny on HIP kernels), or pass '
+                         '--edge canny and the loader derives the edges on the GPU.  Building the mask folder '
+                         "(the reference's vision/setup.py mask: dlib face masks) is out of scope here: run the "
+                         "reference's setup.py for it first, or run with --synthetic"
+                         % (args.data_dir, ', '.join(missing)))
     if not os.path.isfile(args.watermark_file):
         raise SystemExit('the watermark image %s is missing: name one with --watermark-file (an image with an alpha '
                          'channel), or run with --synthetic' % args.watermark_file)
@@ -226,9 +237,9 @@ def main(argv=None):
     else:
         from .datasets import CelebVisionLoader
         train_loader = CelebVisionLoader('train', args.data_dir, args.batch_size, True, device, seed=1234,
-                                         watermark_path=args.watermark_file)
+                                         watermark_path=args.watermark_file, edge=args.edge)
         test_loader = CelebVisionLoader('val', args.data_dir, args.batch_size, False, device,
-                                        watermark_path=args.watermark_file)
+                                        watermark_path=args.watermark_file, edge=args.edge)
         for name, loader in (('train', train_loader), ('val', test_loader)):
             if len(loader) == 0:
                 raise SystemExit('%s lists no image of the %r partition'
