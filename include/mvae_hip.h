@@ -1041,6 +1041,42 @@ int mvae_canny(const uint8_t *src, int channels /* 1: gray [B,H,W]; 3: RGB [B,H,
 int mvae_canny_hysteresis(const uint8_t *cls, uint8_t *edges, int B, int H, int W, mvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * K27  Product of experts of condition rows that each select their own experts, with n draws per row
+ *      (csrc/poe_table.hip).  MVAE.infer (celeba19/model.py:63-89) takes None per modality for the whole batch; a batch
+ *      whose rows condition on different subsets (a sweep over every attribute value, imputing missing attributes) has no
+ *      launch there.  A celeba19 AttributeEncoder reads its {0, 1} input through Embedding(2, 512): in eval mode the 2 * A
+ *      heads of a model are a fixed table, and a row's posterior is a product over a per-row selection from it.
+ *   table     float [A, 2, 2D] contiguous: row (a, v) = expert a's head for input value v, mu in the first D columns,
+ *             logvar in the last D.
+ *   state     int8 [C, A] on the device: -1 attribute absent, 0 / 1 selects table row (a, state).  The caller validates
+ *             (any other value selects nothing: the launch never reads outside the table).
+ *   img_heads float [img_rows, 2D] with row stride ld_img >= 2D, or NULL; img_row int32 [C] on the device: the row of
+ *             img_heads condition c uses, -1 for none; several conditions may name one row.  The caller validates
+ *             -1 <= img_row < img_rows (a value >= img_rows is treated as -1).  With img_heads NULL img_row is not read.
+ *   mu, logvar [C, D], z [n, C, D] contiguous.  PoE variant B as K8-K10 compute it for celeba19: T_e = 1 / (exp(logvar_e) + 1e-8),
+ *             the N(0, 1) prior always an expert, experts added in the order infer stacks them (prior, image, attributes
+ *             ascending), mu = sum mu_e T_e / sum T_e, logvar = log(1 / sum T_e), z = mu + exp(0.5 logvar) * eps.
+ *             n = 0 is legal: mu and logvar only (eval-mode reparametrize: z = mu), z / eps / the counter are not touched.
+ *   eps       [n, C, D] given: used as is.  NULL: generated in the launch -- exactly the standard normals
+ *             mvae_philox_fill(seed, *counter_dev + counter_offset) would write for an [n, C, D] array (the contract of
+ *             mvae_iw_draw and mvae_poe_fwd_draw); the counter is not advanced.  eps_out (nullable) receives the noise used.
+ *   One wave per (condition, slice of 8 draws), lanes along d (D need not be a multiple of 64); the image row and every
+ *   selected table row of a condition are requested before the first is reduced; every slice recomputes the posterior in
+ *   the same fixed order and slice 0 stores it.  No atomics, no scratch: the same inputs give the same bits, and a row's
+ *   values depend neither on C nor on n.
+ *   Refused on the host before any launch (MVAE_ERR_ARG): a null table / state / mu / logvar, A outside
+ *   1..MVAE_POE_TABLE_MAX_A, C or D <= 0, n < 0, n > 8 * 65535, img_heads with a null img_row, img_rows <= 0 or
+ *   ld_img < 2D, n > 0 with a null z or with neither eps nor counter_dev.
+ * ------------------------------------------------------------------------------------ */
+#define MVAE_POE_TABLE_MAX_A 32
+int mvae_poe_table_draw(const float *table, int A, const int8_t *state, const float *img_heads /* nullable */, int ld_img,
+                        int img_rows, const int32_t *img_row /* nullable with img_heads */,
+                        const float *eps /* nullable */, uint64_t seed,
+                        const uint64_t *counter_dev /* nullable with eps or n = 0 */, uint64_t counter_offset,
+                        float *eps_out /* nullable */, float *mu, float *logvar, float *z /* nullable with n = 0 */,
+                        int n, int C, int D, mvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * C1  Gradient exchange of data-parallel replicas -- RCCL over xGMI.
  *     The reference has NO counterpart: it is single-process, single-device (no DataParallel, no
  *     torch.distributed anywhere; README.md:47 `CUDA_VISIBLE_DEVICES=0`).  What this replaces is what N

@@ -93,6 +93,7 @@ class BceSeg(ctypes.Structure):             # mvae_bce_seg
 
 BCE_MULTI_MAX = 8
 IW_FOLD_MAX = 64      # MVAE_IW_FOLD_MAX
+POE_TABLE_MAX_A = 32  # MVAE_POE_TABLE_MAX_A
 
 
 class ExpertGrads(ctypes.Structure):
@@ -239,6 +240,9 @@ _SIGNATURES = {
     'mvae_canny_ws_bytes': (c_size_t, [c_int, c_int, c_int]),
     'mvae_canny': (c_int, [P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, P, P, P, P, c_size_t, P]),
     'mvae_canny_hysteresis': (c_int, [P, P, c_int, c_int, c_int, P]),
+    # K27: the PoE of condition rows that each select their experts from a table, with n draws per row
+    'mvae_poe_table_draw': (c_int, [P, c_int, P, P, c_int, c_int, P, P, c_uint64, P, c_uint64, P, P, P, P, c_int, c_int,
+                                    c_int, P]),
     # C1: the gradient exchange (RCCL bound at run time)
     'mvae_comm_use_library': (c_int, [ctypes.c_char_p]),
     'mvae_comm_rccl_version': (c_int, []),

@@ -1442,8 +1442,97 @@ def iw_fold_rows(lw, rec, sel, state, out=None, finish_k=0):
                                        Kc, B, int(finish_k), _stream()), 'mvae_iw_fold_rows')
 
 
+# ---------------------------------------------------------------------------- PoE of per-row expert selections (K27)
+def poe_table_check(table, state, img_heads=None, img_row=None):
+    """The host checks of ``poe_table_draw`` on the selection itself, before anything is uploaded or launched: returns
+    (state int8 [C, A], img_row int32 [C] or None) as contiguous HOST tensors.  ``ValueError`` names the first defect."""
+    if table.dim() != 3 or table.shape[1] != 2 or table.shape[2] % 2 or table.dtype != torch.float32:
+        raise ValueError('poe_table_draw: table must be float32 [A, 2, 2D] (expert, input value, mu then logvar), '
+                         'got %s %s' % (table.dtype, tuple(table.shape)))
+    A, D = table.shape[0], table.shape[2] // 2
+    if not 1 <= A <= _lib.POE_TABLE_MAX_A:
+        raise ValueError('poe_table_draw: the kernel supports 1 to %d experts in the table, got %d'
+                         % (_lib.POE_TABLE_MAX_A, A))
+    if D < 1 or A * 4 * D >= 2 ** 31 - 1:
+        raise ValueError('poe_table_draw: table of %d experts x %d latents is empty or too large' % (A, D))
+    if not torch.is_tensor(state) or state.is_cuda:
+        raise ValueError('poe_table_draw: state must be a HOST tensor (it is validated here, then uploaded)')
+    if state.dim() != 2 or state.shape[1] != A or state.shape[0] < 1 or state.dtype.is_floating_point \
+            or state.dtype == torch.bool:
+        raise ValueError('poe_table_draw: state must be an integer tensor [C >= 1, %d], got %s %s'
+                         % (A, state.dtype, tuple(state.shape)))
+    bad = ((state < -1) | (state > 1)).nonzero()
+    if bad.numel():
+        c, a = (int(v) for v in bad[0])
+        raise ValueError('poe_table_draw: state[%d, %d] = %d is outside {-1 (absent), 0, 1}' % (c, a, int(state[c, a])))
+    C = state.shape[0]
+    if img_heads is not None and (img_heads.dim() != 2 or img_heads.shape[0] < 1 or img_heads.shape[1] != 2 * D
+                                  or img_heads.dtype != torch.float32 or (D > 0 and img_heads.stride(1) != 1)):
+        raise ValueError('poe_table_draw: img_heads must be float32 [rows >= 1, %d] with unit column stride, got %s %s'
+                         % (2 * D, img_heads.dtype, tuple(img_heads.shape)))
+    if img_row is not None:
+        if not torch.is_tensor(img_row) or img_row.is_cuda or img_row.dim() != 1 or img_row.shape[0] != C \
+                or img_row.dtype.is_floating_point or img_row.dtype == torch.bool:
+            raise ValueError('poe_table_draw: img_row must be a HOST integer tensor [%d]' % C)
+        rows = img_heads.shape[0] if img_heads is not None else 0
+        bad = ((img_row < -1) | (img_row >= max(rows, 0))) & (img_row != -1)
+        if bool(bad.any()):
+            c = int(bad.nonzero()[0])
+            if img_heads is None:
+                raise ValueError('poe_table_draw: img_row[%d] = %d names an image row but img_heads is None'
+                                 % (c, int(img_row[c])))
+            raise ValueError('poe_table_draw: img_row[%d] = %d is outside [-1, %d)' % (c, int(img_row[c]), rows))
+        img_row = img_row.to(torch.int32).contiguous()
+    elif img_heads is not None:
+        raise ValueError('poe_table_draw: img_heads without img_row (which row does each condition use?)')
+    return state.to(torch.int8).contiguous(), img_row
+
+
+def poe_table_draw(table, state, mu, logvar, z=None, img_heads=None, img_row=None, eps=None, seed=0, counter_dev=None,
+                   counter_offset=0, eps_out=None):
+    """The posterior of C condition rows that each select their own experts, and n draws from each, in one launch
+    (mvae_poe_table_draw, K27; PoE variant B with the N(0, 1) prior built in, experts in the order ``infer`` stacks them).
+
+    ``table`` float32 [A, 2, 2D] on the GPU: ``table[a, v]`` = the head of expert a for input value v, mu in the first D
+    columns and logvar in the last D.  ``state`` HOST integer [C, A]: -1 absent, 0 / 1 selects ``table[a, state]``;
+    ``img_heads`` [rows, 2D] (unit column stride, any row stride) or None with ``img_row`` HOST integer [C]: the image row
+    of each condition or -1.  Both are validated on the host (``poe_table_check``) and then uploaded.  Outputs: ``mu``,
+    ``logvar`` [C, D] and ``z`` [n, C, D]; ``z=None`` is n = 0 (the posterior only).  ``eps`` [n, C, D] replays a draw;
+    without it the launch generates what ``philox_fill(seed, counter_dev, counter_offset)`` would write for an [n, C, D]
+    array and (optionally) stores it to ``eps_out``."""
+    state, img_row = poe_table_check(table, state, img_heads, img_row)
+    A, D = table.shape[0], table.shape[2] // 2
+    C = state.shape[0]
+    if tuple(mu.shape) != (C, D) or tuple(logvar.shape) != (C, D):
+        raise ValueError('poe_table_draw: mu and logvar must be [%d, %d], got %s and %s'
+                         % (C, D, tuple(mu.shape), tuple(logvar.shape)))
+    n = 0
+    if z is not None:
+        if z.dim() != 3 or tuple(z.shape[1:]) != (C, D) or z.shape[0] < 1:
+            raise ValueError('poe_table_draw: z must be [n >= 1, %d, %d], got %s' % (C, D, tuple(z.shape)))
+        n = z.shape[0]
+    for t, what in ((eps, 'eps'), (eps_out, 'eps_out')):
+        if t is not None and (z is None or tuple(t.shape) != tuple(z.shape)):
+            raise ValueError('poe_table_draw: %s must have the shape of z%s' % (what, '' if z is None else ' %s' % (tuple(z.shape),)))
+    if n > 8 * 65535:
+        raise ValueError('poe_table_draw: at most %d draws per launch, got %d' % (8 * 65535, n))
+    if n and eps is None and (counter_dev is None or counter_dev.dtype != torch.int64):
+        raise ValueError('poe_table_draw: the device draw needs an int64 launch counter on the GPU')
+    _need_gpu(table, mu, logvar, z, img_heads, eps, counter_dev, eps_out); _f32c(table, mu, logvar, z, eps, eps_out)
+    dev = table.device
+    state_dev = state.to(dev)
+    row_dev = img_row.to(dev) if img_heads is not None else None
+    ld = 0
+    if img_heads is not None:
+        ld = img_heads.stride(0) if img_heads.shape[0] > 1 else max(2 * D, img_heads.stride(0))
+    check(_lib.lib().mvae_poe_table_draw(_ptr(table), A, _ptr(state_dev), _ptr(img_heads), int(ld),
+                                         img_heads.shape[0] if img_heads is not None else 0, _ptr(row_dev), _ptr(eps),
+                                         int(seed), _ptr(counter_dev), int(counter_offset), _ptr(eps_out), _ptr(mu),
+                                         _ptr(logvar), _ptr(z), n, C, D, _stream()), 'mvae_poe_table_draw')
+
+
 # ---------------------------------------------------------------------------- MultiMNIST dataset builder
-MM_DIGIT, MM_CANVAS, MM_MAX_DIGITS, MM_PLAN_STRIDE = 28, 50, 4, 17     # MVAE_MM_* of include/mvae_hip.h
+MM_DIGIT,MM_CANVAS, MM_MAX_DIGITS, MM_PLAN_STRIDE = 28, 50, 4, 17     # MVAE_MM_* of include/mvae_hip.h
 MM_WMIN, MM_WMAX, MM_KSIZE = 7, 50, 9
 _MM_TABLES = {}       # device -> (kk int32 [44, 50, 9], bounds int32 [44, 50, 2]), built once
 
