@@ -550,6 +550,24 @@ int mvae_bce_rowsum_bwd(const float *logits, const float *target, const float *c
                         int R, int P, int rows_per_group, int target_rows,
                         int target_div, int target_row_stride, int target_col_stride,
                         mvae_stream_t stream);
+/* Which kernel mvae_bce_rowsum_fwd / _bwd take for a row of P logits, and how the block kernel walks it -- the functions
+ * the launch and the kernel themselves switch on (csrc/loss.hip bce_block_row + bce_row_vec).  Host only: launches nothing,
+ * allocates nothing, touches no device, holds no state.
+ *   aligned        the row's logits, target, column weights and dlogits pointers are all 16-byte aligned (the kernel decides
+ *                  per row: a target row stride that is no multiple of 4 floats takes some rows off the float4 path)
+ *   has_colw       colw != NULL: weighted rows stay off the batched loop
+ *   batched_trips  (may be NULL) the four-group trips thread 0 of the block makes (no thread makes more); 0 off the float4 path
+ *   tail           (may be NULL) 1 if any thread makes a single-group trip; 0 off the float4 path
+ *   returns        a MVAE_BCEROUTE_* code, or the MVAE_ERR_ARG the launch would return (P <= 0, target_col_stride <= 0;
+ *                  the out-pointers are then left alone).  The launch's other checks are not repeated here. */
+#define MVAE_BCE_BLOCK_MIN_P 512            /* rows of at least this many logits take a block each, shorter ones a wave */
+#define MVAE_BCEROUTE_WAVE               1  /* bce_row_wave_kernel: a wave per row, one element per lane and trip */
+#define MVAE_BCEROUTE_BLOCK_SCALAR       2  /* bce_row_block_kernel, one element per thread and trip (P % 4 != 0, a column
+                                               stride, or an unaligned operand) */
+#define MVAE_BCEROUTE_BLOCK_VEC          3  /* ... float4, single-group trips only */
+#define MVAE_BCEROUTE_BLOCK_VEC_BATCHED  4  /* ... float4, thread 0 makes at least one four-group trip */
+int mvae_bce_route(int P, int target_col_stride, int aligned, int has_colw, int *batched_trips /* may be NULL */,
+                   int *tail /* may be NULL */);
 int mvae_ce_fwd(const float *logits, const int64_t *label, float *row,
                 const float *drow_dev, float *dlogits /* nullable: fused bwd */,
                 int R, int K, int rows_per_group, int label_rows, mvae_stream_t stream);
@@ -581,6 +599,7 @@ int mvae_linear_ce_fwd(const float *x, int ldx, const float *w, const float *bia
  * parts; a part of more than one row per group has at most MVAE_ELBO_MAX_TERMS groups. */
 #define MVAE_ELBO_MAX_PARTS 4
 #define MVAE_ELBO_MAX_TERMS 40
+#define MVAE_ELBO_LONG_GROUP 2048   /* a group of more rows than this is summed by all 16 waves of the block, not by one */
 typedef struct {
     const float *rows;      /* [groups * rows_per_group] */
     const float *coef;      /* per group, device; NULL = 1 */

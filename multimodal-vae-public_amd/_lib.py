@@ -52,6 +52,11 @@ LINEAR_ROUTES = {1: 'gemm2', 2: 'g2s_32x64_k4', 3: 'g2s_64x32_k4', 4: 'g2s_32x64
 BN_ROUTES = {1: 'two_vec_rows', 2: 'two_vec_cols', 3: 'two_scalar', 4: 'fused_vec_g1', 5: 'fused_vec_g2',
              6: 'fused_vec_g3', 7: 'fused_scalar_g1', 8: 'fused_scalar_gn', 9: 'bn1d_g1', 10: 'bn1d_gn', 11: 'slice'}
 
+# mvae_bce_route: the kernels the BCE row-sum launches choose between (MVAE_BCEROUTE_*) and the two thresholds of loss.hip
+BCE_ROUTES = {1: 'wave', 2: 'block_scalar', 3: 'block_vec', 4: 'block_vec_batched'}
+BCE_BLOCK_MIN_P = 512    # MVAE_BCE_BLOCK_MIN_P
+ELBO_LONG_GROUP = 2048   # MVAE_ELBO_LONG_GROUP
+
 
 class Experts(ctypes.Structure):
     _fields_ = [('mu', c_void_p * MAX_EXPERTS), ('logvar', c_void_p * MAX_EXPERTS)]
@@ -153,6 +158,7 @@ _SIGNATURES = {
     'mvae_kl_rows_bwd': (c_int, [P, P, P, P, P, c_int, c_int, P]),
     'mvae_bce_rowsum_fwd': (c_int, [P, P, P, P, P, P] + [c_int] * 7 + [P]),
     'mvae_bce_rowsum_bwd': (c_int, [P, P, P, P, P] + [c_int] * 7 + [P]),
+    'mvae_bce_route': (c_int, [c_int] * 4 + [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     'mvae_ce_fwd': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
     'mvae_ce_bwd': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
     'mvae_group_sums': (c_int, [P, P, P, P, c_int, c_int, c_int, P]),

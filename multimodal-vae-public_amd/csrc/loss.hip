@@ -21,6 +21,13 @@ struct BceArgs {
     int target_div, t_rs, t_cs;   // target row = (r / target_div) % target_rows; element (row, p) at row*t_rs + p*t_cs
 };
 
+// Which kernel a row takes and how the block kernel walks it: bce_launch and the kernels switch on these, mvae_bce_route
+// reports them -- each decision exists once.
+__host__ __device__ __forceinline__ bool bce_block_row(int P) { return P >= MVAE_BCE_BLOCK_MIN_P; }
+// float4 loads / stores of a row (`aligned`: the row's logits, target, column weights and dlogits are all 16-byte aligned)
+__host__ __device__ __forceinline__ bool bce_row_vec(int P, int t_cs, bool aligned) { return P % 4 == 0 && t_cs == 1 && aligned; }
+constexpr int BCE_BATCH = 4;               // float4 groups per batched trip of a thread of bce_row_block_kernel
+
 // One block per row (wide rows: pixels).  Optionally writes the gradient in the same pass.
 __global__ __launch_bounds__(256) void bce_row_block_kernel(BceArgs a) {
     __shared__ float red[16];
@@ -32,15 +39,15 @@ __global__ __launch_bounds__(256) void bce_row_block_kernel(BceArgs a) {
     float *dx = a.dlogits ? a.dlogits + (size_t)r * a.P : nullptr;
     const float dr = (dx && a.drow) ? a.drow[g] : 0.f;
     float s = 0.f;
-    const bool vec = (a.P % 4 == 0) && a.t_cs == 1 && aligned16_dev(x) && aligned16_dev(t) && (!w || aligned16_dev(w)) &&
-                     (!dx || aligned16_dev(dx));
+    const bool vec = bce_row_vec(a.P, a.t_cs, aligned16_dev(x) && aligned16_dev(t) && (!w || aligned16_dev(w)) &&
+                                                  (!dx || aligned16_dev(dx)));
     if (vec) {
         const int p4 = a.P / 4;
         // FOUR float4 groups per trip, all their loads issued before the first is used: one block per row leaves 512 - 2048
         // blocks of 256 threads, and with one dependent load -> exp / log -> store chain per thread the launch moved 75 MB at
         // 2.95 TB/s (image BCE of CelebA, 512 x 12288: profiles/r04_celeba_by_shape.txt); the sums keep their order
         // (element i, i + 256, ... of a thread, as before)
-        constexpr int U = 4;
+        constexpr int U = BCE_BATCH;
         int i = threadIdx.x;
         // (only without column weights -- the image terms: a load under the block-uniform `if (w)` would make hipcc drain the
         //  memory queue behind it and undo the batching; weighted rows take the one-group loop below.  `1.f *` keeps the bits.)
@@ -180,7 +187,7 @@ __device__ __forceinline__ void elbo_reduce_body(const ElboParts &parts, float *
     // group -- one barrier instead of two per group (7 groups of 512 rows: 13 -> 4 us on the MNIST step's
     // critical path).  A LONG group (the per-32-column partials of a folded Bernoulli term: 512 rows x 25) is
     // spread over all 16 waves instead -- one wave would walk it as 200 dependent round trips.
-    constexpr int LONG_GROUP = 2048;
+    constexpr int LONG_GROUP = MVAE_ELBO_LONG_GROUP;
     __shared__ float gsum[MVAE_ELBO_MAX_PARTS * MVAE_ELBO_MAX_TERMS];
     __shared__ float wsum[MVAE_ELBO_MAX_PARTS * MVAE_ELBO_MAX_TERMS][16];
     __shared__ float acc[MVAE_ELBO_MAX_TERMS + 1];
@@ -321,7 +328,7 @@ int bce_launch(BceArgs a, hipStream_t st) {
         return MVAE_ERR_ARG;
     if (!a.rowsum && !a.dlogits) return MVAE_ERR_ARG;
     if (a.dlogits && !a.drow) return MVAE_ERR_ARG;
-    if (a.P >= 512)
+    if (bce_block_row(a.P))
         hipLaunchKernelGGL(bce_row_block_kernel, dim3(a.R), dim3(256), 0, st, a);
     else
         hipLaunchKernelGGL(bce_row_wave_kernel, dim3((a.R + 3) / 4), dim3(256), 0, st, a);
@@ -329,6 +336,28 @@ int bce_launch(BceArgs a, hipStream_t st) {
 }
 
 }  // namespace
+
+// which kernel a row of P logits takes and how: bce_block_row + bce_row_vec, the functions the launch and the kernel go
+// through, and the trip counts of bce_row_block_kernel's two float4 loops.  Pure host code.
+MVAE_EXPORT int mvae_bce_route(int P, int target_col_stride, int aligned, int has_colw, int *batched_trips, int *tail) {
+    if (P <= 0 || target_col_stride <= 0) return MVAE_ERR_ARG;
+    int route = MVAE_BCEROUTE_WAVE, trips = 0, tl = 0;
+    if (bce_block_row(P)) {
+        route = MVAE_BCEROUTE_BLOCK_SCALAR;
+        if (bce_row_vec(P, target_col_stride, aligned != 0)) {
+            // thread i starts at float4 group i and takes a batched trip while i + 256 * (BCE_BATCH - 1) < p4 (never with
+            // column weights), 256 * BCE_BATCH groups further each time, then single groups 256 apart: thread 0 makes the
+            // most batched trips, and some thread is left a single group unless p4 is a whole number of batched trips
+            const int p4 = P / 4, first = 256 * (BCE_BATCH - 1), stride = 256 * BCE_BATCH;
+            trips = (!has_colw && p4 > first) ? (p4 - first - 1) / stride + 1 : 0;
+            tl = (trips == 0 || p4 % stride != 0) ? 1 : 0;
+            route = trips ? MVAE_BCEROUTE_BLOCK_VEC_BATCHED : MVAE_BCEROUTE_BLOCK_VEC;
+        }
+    }
+    if (batched_trips) *batched_trips = trips;
+    if (tail) *tail = tl;
+    return route;
+}
 
 MVAE_EXPORT int mvae_bce_rowsum_fwd(const float *logits, const float *target, const float *colw, float *rowsum,
                                     const float *drow_dev, float *dlogits, int R, int P, int rows_per_group,

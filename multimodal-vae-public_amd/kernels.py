@@ -878,6 +878,20 @@ def bce_rowsum_bwd(logits, target, drow, dlogits, colw=None, rows_per_group=None
                                          target_div, t_rs, t_cs, _stream()), 'mvae_bce_rowsum_bwd')
 
 
+def bce_route(P, aligned=True, target_col_stride=1, colw=False):
+    """(route, batched_trips, tail) of a row of P logits in ``bce_rowsum_fwd`` / ``bce_rowsum_bwd`` -- the name of the kernel
+    and loop it takes (``_lib.BCE_ROUTES``), the four-group trips thread 0 of the block kernel makes and whether any thread
+    makes a single-group trip (both 0 off the float4 path).  ``aligned``: the row's logits, target, column weights and
+    dlogits are all 16-byte aligned; ``colw``: the call has column weights.  Host only (mvae_bce_route: the functions the
+    launch and the kernel themselves switch on).  Raises where the launch would refuse P or the stride."""
+    trips, tail = ctypes.c_int(0), ctypes.c_int(0)
+    rc = _lib.lib().mvae_bce_route(P, target_col_stride, 1 if aligned else 0, 1 if colw else 0, ctypes.byref(trips),
+                                   ctypes.byref(tail))
+    if rc <= 0:
+        check(rc if rc < 0 else -1, 'mvae_bce_route')
+    return _lib.BCE_ROUTES[rc], trips.value, tail.value
+
+
 def _bce_segs(segs, R):
     """[(logits [R,P], target [target_rows,P], dlogits [R,P] or None, weight)] -> (mvae_bce_seg table, target_rows)"""
     if not 0 < len(segs) <= _lib.BCE_MULTI_MAX:
