@@ -1096,6 +1096,59 @@ int mvae_poe_table_draw(const float *table, int A, const int8_t *state, const fl
                         int n, int C, int D, mvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * K28  Label prediction from a trained model (csrc/predict.hip): the Monte-Carlo posterior predictive of the label
+ *      modality, E_{q(z | x)} p(y | z) in the log domain, and its scoring against labels -- the classification accuracy the
+ *      MVAE paper reports beside its log-likelihoods (predict.py).  K20 folds one state per datum; a prediction needs one
+ *      per (datum, class).  Two entry points:
+ *   predict_fold   logits: the label decoder's output on the R = Kc * B sample-major rows of mvae_iw_draw (row r belongs to
+ *                  datum r % B), C logits per row, element (r, c) at logits[r * row_stride + c * col_stride] ([R, C]
+ *                  row-major: (C, 1); the [G, R] block of grouped one-logit heads: (1, R)).
+ *                    MVAE_PREDICT_CATEGORICAL   v[k, b, c] = logits[r, c] - logsumexp_c' logits[r, c']      r = k * B + b
+ *                                               state [B, C, 2], out [B, C]
+ *                    MVAE_PREDICT_BERNOULLI     v[k, b, c, 0] = -softplus(-logits[r, c])   (class 1 first)
+ *                                               v[k, b, c, 1] = -softplus(+logits[r, c])
+ *                                               state [B, C, 2, 2], out [B, C, 2]
+ *                  A state entry is (running maximum, running sum of exp(v - maximum)) over the samples folded so far,
+ *                  merged by K20's rules: the caller initialises it to (-inf, 0), the maximum is subtracted before every
+ *                  exp, a -inf maximum is never subtracted from itself, lanes along k, wave maximum then wave sum.
+ *                  finish_k > 0 (the total number of samples folded, this chunk included) also writes
+ *                  out = maximum + log(sum / finish_k) (the merge's carry and this line are formed in double and
+ *                  rounded once).  A row's log-normaliser is computed once per row with the
+ *                  row's own maximum subtracted (a tile of 256 rows of a datum at a time, kept in LDS); a -inf logit gives
+ *                  v = -inf.  Kc = 1 on a fresh state with finish_k = 1 returns v itself: plain log_softmax /
+ *                  -softplus (the no-sampling path, z = mu, uses the same launch).  Categorical: one block per datum;
+ *                  Bernoulli: one wave per (datum, head).  No atomics, no scratch: the same inputs give the same bits,
+ *                  and a datum's value does not depend on B or, beyond rounding, on how K is cut into chunks.
+ *                  Refused on the host before any launch (MVAE_ERR_ARG): a null logits / state, an unknown mode, R, B or
+ *                  C <= 0, R % B != 0, C > MVAE_PREDICT_MAX_C, a stride <= 0, strides under which two elements alias
+ *                  (neither row_stride > (C - 1) * col_stride nor col_stride > (R - 1) * row_stride), finish_k < 0,
+ *                  finish_k > 0 without out, R * C >= 2^31.
+ *   predict_score  logp: predict_fold's out.  targets: categorical int64 [B]; Bernoulli float {0, 1} [B, C] with row
+ *                  stride target_stride >= C (not read in categorical mode).
+ *                    categorical   pred[b] = argmax_c logp[b, c] (the lowest index on a tie), nll[b] = -logp[b, y_b],
+ *                                  correct[b] = (pred[b] == y_b), confusion [C, C] (truth, prediction) += the counts
+ *                    Bernoulli     pred[b, c] = logp[b, c, 0] > logp[b, c, 1], nll[b, c] = -logp[b, c, 1 - y],
+ *                                  correct[b, c] = (pred == y), confusion [C, 2, 2] (head, truth, prediction) += the counts
+ *                  pred int64, nll float, correct uint8; confusion int64, nullable: the caller zeroes it once and passes
+ *                  it call after call (stream order serialises the calls).  A target outside 0 .. C - 1 (Bernoulli:
+ *                  other than 0 or 1) is counted nowhere, gives nll = +inf and correct = 0, and never indexes the table.
+ *                  targets NULL: predictions only -- nll, correct and confusion must be NULL too.  One block: threads
+ *                  loop over the rows, the counts go to an integer histogram in LDS, then the same block adds it to the
+ *                  table with plain loads and stores.  No global atomics; integer counts: the same bits every run.
+ *                  Refused on the host before any launch (MVAE_ERR_ARG): a null logp / pred, an unknown mode, B or
+ *                  C <= 0, C > MVAE_PREDICT_MAX_C, B * C >= 2^31, targets without nll or correct, nll / correct /
+ *                  confusion without targets, Bernoulli targets with target_stride < C.
+ * ------------------------------------------------------------------------------------ */
+#define MVAE_PREDICT_MAX_C 64
+#define MVAE_PREDICT_CATEGORICAL 0
+#define MVAE_PREDICT_BERNOULLI 1
+int mvae_predict_fold(const float *logits, long long row_stride, long long col_stride, int R, int B, int C, int mode,
+                      float *state, float *out /* nullable */, int finish_k, mvae_stream_t stream);
+int mvae_predict_score(const float *logp, int mode, const void *targets /* nullable */, int target_stride, int B, int C,
+                       int64_t *pred, float *nll /* nullable with targets */, uint8_t *correct /* nullable with targets */,
+                       int64_t *confusion /* nullable */, mvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * C1  Gradient exchange of data-parallel replicas -- RCCL over xGMI.
  *     The reference has NO counterpart: it is single-process, single-device (no DataParallel, no
  *     torch.distributed anywhere; README.md:47 `CUDA_VISIBLE_DEVICES=0`).  What this replaces is what N

@@ -14,13 +14,18 @@ hyphen) or ``importlib.import_module('multimodal-vae-public_amd')``.
     mvae_amd.vision.loglike.log_likelihood(model, data, score=, given=)   the same for the six vision modalities + joint
     mvae_amd.celeba19.loglike.log_likelihood(model, image=, attrs=, score=, given=)   CelebA-19: image, 18 attributes + joint
                                                                       (``from mvae_amd.celeba19 import loglike``)
+    mvae_amd.predict.predict(model, image, given=, n_samples=)        the label the model predicts from the image
+    mvae_amd.predict.evaluate(model, image, label, confusion=)        ... scored: nll, correct, confusion counts
+                                                                      (also ``mvae_amd.predict_label`` / ``mvae_amd.evaluate``)
 """
 from . import _lib, kernels, arena, layers, functional, base, engine, optim, parallel, graph  # noqa: F401
 from .graph import capture_step  # noqa: F401
 from . import loglike  # noqa: F401
 from .loglike import log_likelihood  # noqa: F401
+from . import predict  # noqa: F401
+from .predict import predict as predict_label, evaluate  # noqa: F401  (``predict`` itself names the module)
 from . import mnist, fashionmnist, celeba, celeba19  # noqa: F401
 
 __all__ = ['kernels', 'arena', 'layers', 'functional', 'base', 'engine', 'optim', 'parallel', 'graph', 'capture_step',
-           'loglike', 'log_likelihood',
+           'loglike', 'log_likelihood', 'predict', 'predict_label', 'evaluate',
            'mnist', 'fashionmnist', 'celeba', 'celeba19']

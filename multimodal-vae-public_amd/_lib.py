@@ -99,6 +99,8 @@ class BceSeg(ctypes.Structure):             # mvae_bce_seg
 BCE_MULTI_MAX = 8
 IW_FOLD_MAX = 64      # MVAE_IW_FOLD_MAX
 POE_TABLE_MAX_A = 32  # MVAE_POE_TABLE_MAX_A
+PREDICT_MAX_C = 64    # MVAE_PREDICT_MAX_C
+PREDICT_CATEGORICAL, PREDICT_BERNOULLI = 0, 1      # MVAE_PREDICT_*
 
 
 class ExpertGrads(ctypes.Structure):
@@ -249,6 +251,9 @@ _SIGNATURES = {
     # K27: the PoE of condition rows that each select their experts from a table, with n draws per row
     'mvae_poe_table_draw': (c_int, [P, c_int, P, P, c_int, c_int, P, P, c_uint64, P, c_uint64, P, P, P, P, c_int, c_int,
                                     c_int, P]),
+    # K28: label prediction (the fold of one state per (datum, class), and the scoring against labels)
+    'mvae_predict_fold': (c_int, [P, ctypes.c_longlong, ctypes.c_longlong, c_int, c_int, c_int, c_int, P, P, c_int, P]),
+    'mvae_predict_score': (c_int, [P, c_int, P, c_int, c_int, c_int, P, P, P, P, P]),
     # C1: the gradient exchange (RCCL bound at run time)
     'mvae_comm_use_library': (c_int, [ctypes.c_char_p]),
     'mvae_comm_rccl_version': (c_int, []),

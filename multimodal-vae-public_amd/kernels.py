@@ -1615,3 +1615,92 @@ def multimnist_compose(bank, plan):
     check(_lib.lib().mvae_multimnist_compose(_ptr(bank), int(bank.shape[0]), _ptr(plan_dev), M, _ptr(kk), _ptr(bounds),
                                              _ptr(canvas), _ptr(flags), _stream()), 'mvae_multimnist_compose')
     return canvas, flags
+
+
+# ---------------------------------------------------------------------------- label prediction (K28)
+PREDICT_MODES = {'categorical': _lib.PREDICT_CATEGORICAL, 'bernoulli': _lib.PREDICT_BERNOULLI}
+
+
+def _predict_mode(mode, who):
+    if mode not in PREDICT_MODES:
+        raise RuntimeError("%s: mode must be 'categorical' or 'bernoulli', got %r" % (who, mode))
+    return PREDICT_MODES[mode]
+
+
+def fresh_predict_state(B, C, mode, device):
+    """An empty state for ``predict_fold``: (maximum, sum) = (-inf, 0) per (datum, class) -- [B, C, 2] categorical,
+    [B, C, 2, 2] Bernoulli (class 1 first)."""
+    _predict_mode(mode, 'fresh_predict_state')
+    shape = (int(B), int(C), 2) if mode == 'categorical' else (int(B), int(C), 2, 2)
+    state = torch.zeros(shape, dtype=torch.float32, device=device)
+    state[..., 0] = float('-inf')
+    return state
+
+
+def predict_fold(logits, B, mode, state, out=None, finish_k=0):
+    """Fold the chunk ``logits`` [Kc * B, C] (sample-major rows, row r belongs to datum r % B; any two strides under which
+    no two elements alias, so the transpose of a [G, R] block qualifies) into ``state`` (``fresh_predict_state``) --
+    mvae_predict_fold.  ``finish_k`` = the total number of samples folded so far, this chunk included, also writes
+    ``out`` ([B, C] categorical, [B, C, 2] Bernoulli: log p(1), log p(0)) = logsumexp over the samples - log(finish_k)."""
+    code = _predict_mode(mode, 'predict_fold')
+    _need_gpu(logits, state, out); _f32c(state, out)
+    if logits.dtype != torch.float32 or logits.dim() != 2:
+        raise RuntimeError('predict_fold: logits must be float32 [Kc * B, C], got %s %s' % (logits.dtype, tuple(logits.shape)))
+    R, C = logits.shape
+    B = int(B)
+    tail = (2,) if mode == 'categorical' else (2, 2)
+    if B < 1 or R < 1 or R % B != 0 or not 1 <= C <= _lib.PREDICT_MAX_C:
+        raise RuntimeError('predict_fold: %d rows of %d logits for %d data (rows a positive multiple of the data, at most '
+                           '%d classes)' % (R, C, B, _lib.PREDICT_MAX_C))
+    if tuple(state.shape) != (B, C) + tail:
+        raise RuntimeError('predict_fold: state must be %s, got %s' % ((B, C) + tail, tuple(state.shape)))
+    rs = logits.stride(0) if R > 1 else 1           # an axis of extent 1: torch's stride for it means nothing
+    cs = logits.stride(1) if C > 1 else 1
+    if rs < 1 or cs < 1 or (rs <= (C - 1) * cs and cs <= (R - 1) * rs):
+        raise RuntimeError('predict_fold: the strides %s of logits %s make elements alias' % (logits.stride(), (R, C)))
+    if finish_k and (out is None or tuple(out.shape) != (B, C) + tail[1:]):
+        raise RuntimeError('predict_fold: finish needs out %s' % ((B, C) + tail[1:],))
+    check(_lib.lib().mvae_predict_fold(_ptr(logits), int(rs), int(cs), R, B, C, code, _ptr(state), _ptr(out), int(finish_k),
+                                       _stream()), 'mvae_predict_fold')
+
+
+def predict_score(logp, mode, pred, targets=None, nll=None, correct=None, confusion=None):
+    """Predictions from ``predict_fold``'s ``out`` and, with ``targets``, their score (mvae_predict_score): ``pred`` int64,
+    ``nll`` float32 and ``correct`` uint8, each [B] categorical / [B, C] Bernoulli; ``targets`` int64 [B] / float {0, 1}
+    [B, C] with unit column stride; the counts are ADDED into ``confusion`` (int64 [C, C] (truth, prediction) /
+    [C, 2, 2]; zero it once).  A target out of range is counted nowhere (nll = +inf, correct = 0)."""
+    code = _predict_mode(mode, 'predict_score')
+    _need_gpu(logp, pred, targets, nll, correct, confusion); _f32c(logp, nll)
+    cat = mode == 'categorical'
+    if logp.dim() != (2 if cat else 3) or (not cat and logp.shape[2] != 2):
+        raise RuntimeError('predict_score: logp must be %s, got %s' % ('[B, C]' if cat else '[B, C, 2]', tuple(logp.shape)))
+    B, C = logp.shape[:2]
+    if B < 1 or not 1 <= C <= _lib.PREDICT_MAX_C:
+        raise RuntimeError('predict_score: %d data of %d classes (at most %d)' % (B, C, _lib.PREDICT_MAX_C))
+    shape = (B,) if cat else (B, C)
+    for t, name, dtype in ((pred, 'pred', torch.int64), (nll, 'nll', torch.float32), (correct, 'correct', torch.uint8)):
+        if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise RuntimeError('predict_score: %s must be a contiguous %s %s' % (name, dtype, shape))
+    if pred is None:
+        raise RuntimeError('predict_score: pred is required')
+    ldt = 0
+    if targets is None:
+        if nll is not None or correct is not None or confusion is not None:
+            raise RuntimeError('predict_score: nll, correct and confusion need targets')
+    else:
+        if nll is None or correct is None:
+            raise RuntimeError('predict_score: targets need nll and correct')
+        if cat:
+            if targets.dtype != torch.int64 or tuple(targets.shape) != (B,) or not targets.is_contiguous():
+                raise RuntimeError('predict_score: categorical targets must be a contiguous int64 [%d]' % B)
+        else:
+            if targets.dtype != torch.float32 or tuple(targets.shape) != (B, C) or (C > 1 and targets.stride(1) != 1) \
+                    or (B > 1 and targets.stride(0) < C):
+                raise RuntimeError('predict_score: Bernoulli targets must be float32 [%d, %d] with unit column stride' % (B, C))
+            ldt = targets.stride(0) if B > 1 else max(C, targets.stride(0))
+        want = (C, C) if cat else (C, 2, 2)
+        if confusion is not None and (confusion.dtype != torch.int64 or tuple(confusion.shape) != want
+                                      or not confusion.is_contiguous()):
+            raise RuntimeError('predict_score: confusion must be a contiguous int64 %s' % (want,))
+    check(_lib.lib().mvae_predict_score(_ptr(logp), code, _ptr(targets), int(ldt), B, C, _ptr(pred), _ptr(nll),
+                                        _ptr(correct), _ptr(confusion), _stream()), 'mvae_predict_score')
