@@ -52,7 +52,7 @@ import torch  # noqa: E402
 from .. import kernels as K  # noqa: E402
 from .. import layers as L  # noqa: E402
 from ..celeba.datasets import ATTR_IX_TO_KEEP, IX_TO_ATTR_DICT  # noqa: E402
-from ..vision.loglike import fresh_state, report  # noqa: E402
+from ..draws import check_draws, draw_chunks, eval_mode, fresh_state, names, report, require_gpu  # noqa: E402
 from .model import N_ATTRS  # noqa: E402
 
 ATTRIBUTES = tuple(IX_TO_ATTR_DICT[ATTR_IX_TO_KEEP[i]] for i in range(N_ATTRS))
@@ -64,21 +64,8 @@ N_ROWS = 1 + N_ATTRS                 # loss rows per sample: the image's, then o
 
 
 def _names(value, what, default):
-    if value is None:
-        value = default
-    names = (value,) if isinstance(value, str) else tuple(value)
-    out = []
-    for n in names:
-        if n == 'attrs':
-            out.extend(ATTRIBUTES)
-        elif n in MODALITIES:
-            out.append(n)
-        else:
-            raise ValueError("celeba19 log_likelihood: unknown modality %r in `%s` (the modalities are %s; 'attrs' names "
-                             "the 18 attributes)" % (n, what, ', '.join(MODALITIES)))
-    if not out:
-        raise ValueError('celeba19 log_likelihood: `%s` must name at least one modality' % what)
-    return tuple(m for m in MODALITIES if m in out)
+    return names(value, what, MODALITIES, 'celeba19 log_likelihood', default=default, aliases={'attrs': ATTRIBUTES},
+                 hint="the modalities are %s; 'attrs' names the 18 attributes" % ', '.join(MODALITIES))
 
 
 def _check(model, image, attrs, score, given, n_samples, chunk_rows, eps, path):
@@ -103,20 +90,12 @@ def _check(model, image, attrs, score, given, n_samples, chunk_rows, eps, path):
     B = (image if used_image else attrs).shape[0]
     if B < 1:
         raise ValueError('celeba19 log_likelihood: no data (B = 0)')
-    if int(n_samples) < 1:
-        raise ValueError('celeba19 log_likelihood: n_samples must be at least 1 (got %r)' % (n_samples,))
-    if int(chunk_rows) < 1:
-        raise ValueError('celeba19 log_likelihood: chunk_rows must be at least 1 (got %r)' % (chunk_rows,))
-    if eps is not None and tuple(eps.shape) != (int(n_samples), B, model.n_latents):
-        raise ValueError('celeba19 log_likelihood: eps must be [n_samples, B, D] = %s, got %s'
-                         % ((int(n_samples), B, model.n_latents), tuple(eps.shape)))
+    check_draws('celeba19 log_likelihood', n_samples, chunk_rows, eps, B, model.n_latents)
     if path is None:
         path = DEFAULT_PATH
     if path not in PATHS:
         raise ValueError('celeba19 log_likelihood: path must be one of %s, got %r' % (', '.join(PATHS), path))
-    if not next(model.parameters()).is_cuda:
-        raise RuntimeError('celeba19 log_likelihood: the model must live on the GPU (model.cuda()); the HIP path has no '
-                           'CPU fallback')
+    require_gpu('celeba19 log_likelihood', model)
     return score, given, path, B
 
 
@@ -193,8 +172,6 @@ def chunk_loop(model, mu, logvar, image, attrs, score, n_samples, Kc, eps=None, 
     sel = [MODALITIES.index(n) for n in score]                  # rows of the loss-row buffer: 0 image, 1 + i attribute i
     sel_dev = torch.tensor(sel, dtype=torch.int64, device=dev)
     scored_attrs = [s - 1 for s in sel if s > 0]
-    z = torch.empty(Kc, B, D, dtype=torch.float32, device=dev)
-    lw = torch.empty(Kc, B, dtype=torch.float32, device=dev)
     rec_flat = torch.empty(N_ROWS * Kc * B, dtype=torch.float32, device=dev)
     experts = targets = logits_flat = None
     if scored_attrs:
@@ -206,16 +183,10 @@ def chunk_loop(model, mu, logvar, image, attrs, score, n_samples, Kc, eps=None, 
             targets = {}                                        # samples in the chunk -> [G, n * B]
     state = fresh_state(S + 1, B, dev)
     out = torch.empty(S + 1, B, dtype=torch.float32, device=dev)
-    counter = torch.zeros(1, dtype=torch.int64, device=dev) if eps is None else None
     fold = FOLDS[path]
-    for c, k0 in enumerate(range(0, n_samples, Kc)):
-        n = min(Kc, n_samples - k0)
+    for zc, lwc, finish_k in draw_chunks(mu, logvar, n_samples, Kc, eps=eps, seed=seed):
+        n = zc.shape[0]
         R = n * B
-        zc, lwc = z[:n], lw[:n]
-        if eps is not None:
-            K.iw_draw(mu, logvar, zc, lwc, eps=eps[k0:k0 + n].to(dev).float().contiguous())
-        else:
-            K.iw_draw(mu, logvar, zc, lwc, seed=seed, counter_dev=counter, counter_offset=c)
         zr = zc.view(R, D)
         rec = rec_flat[:N_ROWS * R].view(N_ROWS, R)             # dense for this chunk's R: every row range is contiguous
         if 'image' in score:
@@ -230,7 +201,7 @@ def chunk_loop(model, mu, logvar, image, attrs, score, n_samples, Kc, eps=None, 
                 if n not in targets:
                     targets[n] = cols.t().unsqueeze(1).expand(experts.G, n, B).reshape(experts.G, R).contiguous()
                 experts.rec_rows(h, targets[n], block, logits_flat[:experts.G * R].view(experts.G, R, 1))
-        fold(lwc, rec, sel, sel_dev, state, out, n_samples if k0 + n == n_samples else 0)
+        fold(lwc, rec, sel, sel_dev, state, out, finish_k)
     return out
 
 
@@ -262,17 +233,10 @@ def log_likelihood(model, image=None, attrs=None, score=None, given=None, n_samp
         image = image.to(dev).float().contiguous()
     if attrs is not None and any(n != 'image' for n in score + given):
         attrs = attrs.to(dev).float().contiguous()
-    modes = [(m, m.training) for m in model.modules()]
-    model.eval()
-    try:
-        with torch.no_grad():
-            mu, logvar = infer(model, image, attrs, given)
-            out = chunk_loop(model, mu, logvar, image.reshape(B, -1) if 'image' in score else None, attrs, score,
-                             n_samples, max(1, int(chunk_rows) // B), eps=eps, seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
-                             path=path)
-    finally:
-        for m, mode in modes:
-            m.training = mode
+    with eval_mode(model):
+        mu, logvar = infer(model, image, attrs, given)
+        out = chunk_loop(model, mu, logvar, image.reshape(B, -1) if 'image' in score else None, attrs, score, n_samples,
+                         max(1, int(chunk_rows) // B), eps=eps, seed=int(seed) & 0xFFFFFFFFFFFFFFFF, path=path)
     if not per_modality:
         return out[len(score)]
     res = {name: out[i] for i, name in enumerate(score)}

@@ -32,6 +32,7 @@ import torch  # noqa: E402
 
 from .. import kernels as K  # noqa: E402
 from .. import layers as L  # noqa: E402
+from ..draws import eval_mode  # noqa: E402
 from .loglike import ATTRIBUTES, AttrExperts  # noqa: E402
 from .model import N_ATTRS  # noqa: E402
 
@@ -95,25 +96,19 @@ def expert_table(model):
         raise RuntimeError('celeba19 sample: the attribute encoders are not Embedding + Swish, Linear + Swish, Linear')
     dev = next(model.parameters()).device
     G = gp.G
-    modes = [(m, m.training) for m in model.attr_encoders.modules()]
-    model.attr_encoders.eval()
-    try:
-        with torch.no_grad():
-            values = torch.tensor([[0.0] * G, [1.0] * G], dtype=torch.float32, device=dev)       # [2 rows, G]
-            w0, w_gs, _, _ = gp.layer(0)
-            if w0.shape[0] != 2:
-                raise RuntimeError('celeba19 sample: the attribute encoders must start with Embedding(2, .)')
-            h = torch.empty(G, 2, w0.shape[1], dtype=torch.float32, device=dev)
-            K.embedding_swish_fwd_grouped(values, w0, w_gs, h)
-            w0, w_gs, b0, b_gs = gp.layer(1)
-            a = torch.empty(G, 2, w0.shape[0], dtype=torch.float32, device=dev)
-            K.linear_fwd_grouped(h, w0, w_gs, b0, b_gs, None, a)
-            w0, w_gs, b0, b_gs = gp.layer(2)
-            table = torch.empty(G, 2, w0.shape[0], dtype=torch.float32, device=dev)
-            K.linear_fwd_grouped(a, w0, w_gs, b0, b_gs, table, None)
-    finally:
-        for m, mode in modes:
-            m.training = mode
+    with eval_mode(model.attr_encoders):
+        values = torch.tensor([[0.0] * G, [1.0] * G], dtype=torch.float32, device=dev)       # [2 rows, G]
+        w0, w_gs, _, _ = gp.layer(0)
+        if w0.shape[0] != 2:
+            raise RuntimeError('celeba19 sample: the attribute encoders must start with Embedding(2, .)')
+        h = torch.empty(G, 2, w0.shape[1], dtype=torch.float32, device=dev)
+        K.embedding_swish_fwd_grouped(values, w0, w_gs, h)
+        w0, w_gs, b0, b_gs = gp.layer(1)
+        a = torch.empty(G, 2, w0.shape[0], dtype=torch.float32, device=dev)
+        K.linear_fwd_grouped(h, w0, w_gs, b0, b_gs, None, a)
+        w0, w_gs, b0, b_gs = gp.layer(2)
+        table = torch.empty(G, 2, w0.shape[0], dtype=torch.float32, device=dev)
+        K.linear_fwd_grouped(a, w0, w_gs, b0, b_gs, table, None)
     if table.shape[2] != 2 * model.n_latents:
         raise RuntimeError('celeba19 sample: the attribute encoders must end in Linear(., 2 * n_latents)')
     return table
@@ -216,31 +211,25 @@ def generate(model, image=None, img_row=None, state=None, n_samples=64, eps=None
     state, img_row = _check(model, image, img_row, state, n_samples, eps)
     n, C, D = int(n_samples), state.shape[0], model.n_latents
     dev = next(model.parameters()).device
-    modes = [(m, m.training) for m in model.modules()]
-    model.eval()
-    try:
-        with torch.no_grad():
-            table = expert_table(model)
-            heads = None
-            if img_row is not None:
-                heads = model.image_encoder.heads(image.to(dev).float().contiguous())
-            mu = torch.empty(C, D, dtype=torch.float32, device=dev)
-            logvar = torch.empty_like(mu)
-            z = torch.empty(n, C, D, dtype=torch.float32, device=dev) if n else None
-            if n and eps is not None:
-                K.poe_table_draw(table, state, mu, logvar, z, img_heads=heads, img_row=img_row,
-                                 eps=eps.to(dev).float().contiguous())
-            else:
-                counter = torch.zeros(1, dtype=torch.int64, device=dev) if n else None
-                K.poe_table_draw(table, state, mu, logvar, z, img_heads=heads, img_row=img_row,
-                                 seed=int(seed) & 0xFFFFFFFFFFFFFFFF, counter_dev=counter)
-            if z is None:
-                z = mu.view(1, C, D)
-            probs_image, probs_attrs = decode(model, z.reshape(-1, D))
-    finally:
-        for m, mode in modes:
-            m.training = mode
-    lead = z.shape[0]
+    with eval_mode(model):
+        table = expert_table(model)
+        heads = None
+        if img_row is not None:
+            heads = model.image_encoder.heads(image.to(dev).float().contiguous())
+        mu = torch.empty(C, D, dtype=torch.float32, device=dev)
+        logvar = torch.empty_like(mu)
+        z = torch.empty(n, C, D, dtype=torch.float32, device=dev) if n else None
+        if n and eps is not None:
+            K.poe_table_draw(table, state, mu, logvar, z, img_heads=heads, img_row=img_row,
+                             eps=eps.to(dev).float().contiguous())
+        else:
+            counter = torch.zeros(1, dtype=torch.int64, device=dev) if n else None
+            K.poe_table_draw(table, state, mu, logvar, z, img_heads=heads, img_row=img_row,
+                             seed=int(seed) & 0xFFFFFFFFFFFFFFFF, counter_dev=counter)
+        if z is None:
+            z = mu.view(1, C, D)
+        probs_image, probs_attrs = decode(model, z.reshape(-1, D))
+    lead =z.shape[0]
     return {'mu': mu, 'logvar': logvar, 'z': z, 'image': probs_image.view((lead, C) + IMAGE_SHAPE),
             'attrs': probs_attrs.view(lead, C, N_ATTRS)}
 

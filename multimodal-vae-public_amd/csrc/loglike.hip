@@ -5,10 +5,10 @@
 // kernels (loss.hip) run on the K*B rows these two launches sit around:
 //   iw_draw_kernel        z[k, b, :] = mu[b, :] + exp(0.5 logvar[b, :]) * eps[k, b, :]  and the density-ratio row
 //                         lw[k, b] = sum_d 0.5 eps^2 - 0.5 z^2 + 0.5 logvar   (= log p(z) - log q(z | x); the 2 pi cancel)
-//   iw_accumulate_kernel  the streaming log-mean-exp over k of lw[k, b] - (reconstruction rows of sample (k, b)).
+//   iw_accumulate_kernel  the streaming log-mean-exp (iw_fold.h) over k of lw[k, b] - (reconstruction rows of sample (k, b)).
 // Both are HBM- / latency-bound element work: one wave per row, lanes along the reduced index, wave reductions in a
 // fixed order (deterministic, no atomics, no LDS).
-#include "common.h"
+#include "iw_fold.h"
 #include "philox.h"
 
 namespace {
@@ -63,32 +63,10 @@ __device__ __forceinline__ float iw_logw(const IwAccArgs &a, int k, int b) {
     return v;
 }
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
 __global__ __launch_bounds__(IW_THREADS) void iw_accumulate_kernel(IwAccArgs a) {
-    const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * (IW_THREADS / 64) + (threadIdx.x >> 6);
-    if (b >= a.B) return;
-    float m = -INFINITY;
-    for (int k = lane; k < a.Kc; k += 64) m = fmaxf(m, iw_logw(a, k, b));
-    m = wave_max(m);
-    const float m_old = a.state[2 * b], s_old = a.state[2 * b + 1];
-    const float m_new = fmaxf(m_old, m);
-    float s = 0.f;
-    // a maximum of -inf (an empty state, or a chunk of -inf weights) carries no mass: never form -inf - (-inf)
-    if (m_new != -INFINITY)
-        for (int k = lane; k < a.Kc; k += 64) s += expf(iw_logw(a, k, b) - m_new);
-    s = wave_sum(s);
-    if (m_old != -INFINITY) s += s_old * expf(m_old - m_new);
-    if (lane == 0) {
-        a.state[2 * b] = m_new;
-        a.state[2 * b + 1] = s;
-        if (a.finish_k > 0) a.out[b] = m_new + logf(s) - logf((float)a.finish_k);
-    }
+    if (b >= a.B) return;                              // whole waves exit together; no block barrier below
+    iw_fold_wave([&](int k) { return iw_logw(a, k, b); }, a.Kc, a.state + 2 * b, a.out + b, a.finish_k);
 }
 
 }  // namespace

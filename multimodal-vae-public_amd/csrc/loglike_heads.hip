@@ -13,12 +13,11 @@
 //                           launch is HBM-bound: the rows of a wave are all requested before the first is reduced.
 //   iw_fold_rows_kernel     K24's fold for row sums that already exist: one wave per (state, datum), lanes along k.  State
 //                           j < S takes lw - rec[sel[j]], state S takes lw - (rec[sel[0]] + ... + rec[sel[S-1]]) added in
-//                           j order, merged by the rules of iw_accumulate_kernel (loglike.hip): wave maximum, then wave sum
-//                           of exp(. - maximum); a -inf maximum is never subtracted from itself.
+//                           j order, merged with iw_fold_wave (iw_fold.h), the fold of iw_accumulate_kernel (loglike.hip).
 // No atomics, no scratch, fixed reduction orders: the same inputs give the same bits, and a row's value depends neither on
 // R nor on the grid.
 #include <type_traits>
-#include "common.h"
+#include "iw_fold.h"
 
 namespace {
 
@@ -103,12 +102,6 @@ struct FoldRowsArgs {
     int Kc, B, finish_k;
 };
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
 // The log-weight of sample (k, b) for state j: a marginal takes its own row, the joint (j == S) all of them in j order.
 // One row's term passes through the same 0 + rec, so with S == 1 the two states hold the same bits.
 __device__ __forceinline__ float fold_rows_logw(const FoldRowsArgs &a, int k, int b, int j) {
@@ -120,27 +113,11 @@ __device__ __forceinline__ float fold_rows_logw(const FoldRowsArgs &a, int k, in
 }
 
 __global__ __launch_bounds__(FOLD_THREADS) void iw_fold_rows_kernel(FoldRowsArgs a) {
-    const int lane = threadIdx.x & 63;
     const long long w = (long long)blockIdx.x * (FOLD_THREADS / 64) + (threadIdx.x >> 6);
     if (w >= (long long)(a.S + 1) * a.B) return;            // whole waves exit together; no block barrier below
     const int j = (int)(w / a.B), b = (int)(w - (long long)j * a.B);
-    float m = -INFINITY;
-    for (int k = lane; k < a.Kc; k += 64) m = fmaxf(m, fold_rows_logw(a, k, b, j));
-    m = wave_max(m);
-    float *st = a.state + 2 * (size_t)w;                    // state [S + 1, B, 2], out [S + 1, B]: w = j * B + b
-    const float m_old = st[0], s_old = st[1];
-    const float m_new = fmaxf(m_old, m);
-    float s = 0.f;
-    // a maximum of -inf (an empty state, or a chunk of -inf weights) carries no mass: never form -inf - (-inf)
-    if (m_new != -INFINITY)
-        for (int k = lane; k < a.Kc; k += 64) s += expf(fold_rows_logw(a, k, b, j) - m_new);
-    s = wave_sum(s);
-    if (m_old != -INFINITY) s += s_old * expf(m_old - m_new);
-    if (lane == 0) {
-        st[0] = m_new;
-        st[1] = s;
-        if (a.finish_k > 0) a.out[w] = m_new + logf(s) - logf((float)a.finish_k);
-    }
+    // state [S + 1, B, 2], out [S + 1, B]: w = j * B + b
+    iw_fold_wave([&](int k) { return fold_rows_logw(a, k, b, j); }, a.Kc, a.state + 2 * (size_t)w, a.out + w, a.finish_k);
 }
 
 }  // namespace

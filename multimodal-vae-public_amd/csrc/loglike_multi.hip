@@ -13,13 +13,12 @@
 //                           unweighted partial in scratch.  HBM-bound: it reads every logit once.
 //   iw_fold_multi_kernel    one wave per (state, datum), lanes along k.  A lane adds its sample's partials per segment in
 //                           index order -- the per-segment row sums live in registers only, there is no [S, R] array --
-//                           forms its state's log-weight and the wave merges it into the state by the rules of
-//                           iw_accumulate_kernel (loglike.hip): wave maximum, then wave sum of exp(. - maximum); a -inf
-//                           maximum is never subtracted from itself.  (One wave per datum carrying all S + 1 states in
+//                           forms its state's log-weight and the wave merges it into the state with iw_fold_wave
+//                           (iw_fold.h), the fold of iw_accumulate_kernel (loglike.hip).  (One wave per datum carrying all S + 1 states in
 //                           registers computes the same bits; at B = 8, S = 6 it measured 0.001 - 0.004 ms behind at
 //                           Kc = 128 and 256 and level at 512, profiles/vision_loglike.txt, and was not kept.)
 // No atomics, fixed reduction orders: the same inputs give the same bits.
-#include "common.h"
+#include "iw_fold.h"
 
 namespace {
 
@@ -86,12 +85,6 @@ struct FoldArgs {
     int Kc, B, finish_k;
 };
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
 // reconstruction term of segment s for the sample whose partials start at p: its chunks added in index order
 __device__ __forceinline__ float seg_rec(const FoldArgs &a, const float *p, int s) {
     float rec = 0.f;
@@ -111,28 +104,12 @@ __device__ __forceinline__ float fold_logw(const FoldArgs &a, int k, int b, int 
 }
 
 __global__ __launch_bounds__(FOLD_THREADS) void iw_fold_multi_kernel(FoldArgs a) {
-    const int lane = threadIdx.x & 63;
     // (n + 1) * B can pass 2^31 while Kc * B and R * chunks-per-row do not
     const long long w = (long long)blockIdx.x * (FOLD_THREADS / 64) + (threadIdx.x >> 6);
     if (w >= (long long)(a.n + 1) * a.B) return;            // whole waves exit together; no block barrier below
     const int j = (int)(w / a.B), b = (int)(w - (long long)j * a.B);
-    float m = -INFINITY;
-    for (int k = lane; k < a.Kc; k += 64) m = fmaxf(m, fold_logw(a, k, b, j));
-    m = wave_max(m);
-    float *st = a.state + 2 * (size_t)w;                    // state [n + 1, B, 2], out [n + 1, B]: w = j * B + b
-    const float m_old = st[0], s_old = st[1];
-    const float m_new = fmaxf(m_old, m);
-    float s = 0.f;
-    // a maximum of -inf (an empty state, or a chunk of -inf weights) carries no mass: never form -inf - (-inf)
-    if (m_new != -INFINITY)
-        for (int k = lane; k < a.Kc; k += 64) s += expf(fold_logw(a, k, b, j) - m_new);
-    s = wave_sum(s);
-    if (m_old != -INFINITY) s += s_old * expf(m_old - m_new);
-    if (lane == 0) {
-        st[0] = m_new;
-        st[1] = s;
-        if (a.finish_k > 0) a.out[w] = m_new + logf(s) - logf((float)a.finish_k);
-    }
+    // state [n + 1, B, 2], out [n + 1, B]: w = j * B + b
+    iw_fold_wave([&](int k) { return fold_logw(a, k, b, j); }, a.Kc, a.state + 2 * (size_t)w, a.out + w, a.finish_k);
 }
 
 // argument checks of the table and the chunk plan; *cpr_out = chunks per row (0 on a table the launch refuses)

@@ -7,7 +7,7 @@
 //   predict_score_kernel  arg-max, -logp of the true class, correct flag and the confusion counts, in one block.
 // Element / latency-bound work on a few thousand logits: lanes along k, wave reductions in a fixed order (deterministic,
 // no global atomics, no scratch).
-#include "common.h"
+#include "iw_fold.h"          // wave_max; the float fold of that header is not this unit's merge (pf_merge below)
 
 namespace {
 
@@ -23,12 +23,6 @@ struct FoldArgs {
     long long rs, cs;                               // element (r, c) at r * rs + c * cs
     int Kc, B, C, finish_k;
 };
-
-__device__ __forceinline__ float pf_wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
 
 __device__ __forceinline__ float pf_logit(const FoldArgs &a, int k, int b, int c) {
     return a.logits[((size_t)k * a.B + b) * (size_t)a.rs + (size_t)c * (size_t)a.cs];
@@ -90,7 +84,7 @@ __global__ __launch_bounds__(PF_THREADS) void predict_fold_cat_kernel(FoldArgs a
                     }
                     m = fmaxf(m, v[i]);
                 }
-                m = pf_wave_max(m);
+                m = wave_max(m);
                 const float m_new = fmaxf(m_run[j], m);
                 float s = 0.f;
                 if (m_new != -INFINITY) {
@@ -132,7 +126,7 @@ __global__ __launch_bounds__(PF_THREADS) void predict_fold_bern_kernel(FoldArgs 
         m1 = fmaxf(m1, pf_neg_softplus(-l));
         m0 = fmaxf(m0, pf_neg_softplus(l));
     }
-    m1 = pf_wave_max(m1); m0 = pf_wave_max(m0);
+    m1 = wave_max(m1); m0 = wave_max(m0);
     float *st = a.state + (size_t)idx * 4;
     const float m1_old = st[0], s1_old = st[1], m0_old = st[2], s0_old = st[3];
     const float m1_new = fmaxf(m1_old, m1), m0_new = fmaxf(m0_old, m0);

@@ -23,22 +23,17 @@ launch (streaming log-mean-exp).  ``celeba19`` (19 modalities) is refused here: 
 import torch
 
 from . import kernels as K
+from .draws import check_draws, draw_chunks, eval_mode, fresh_state, names, report, require_gpu
 
 MODALITIES = ('image', 'label')
 KINDS = ('mnist', 'fashionmnist', 'celeba', 'multimnist')
 
 
 def _names(value, what):
-    names = (value,) if isinstance(value, str) else tuple(value)
-    for n in names:
-        if n not in MODALITIES:
-            raise ValueError("log_likelihood: unknown modality %r in `%s` (use 'image' and / or 'label')" % (n, what))
-    if not names:
-        raise ValueError('log_likelihood: `%s` must name at least one modality' % what)
-    return tuple(m for m in MODALITIES if m in names)
+    return names(value, what, MODALITIES, 'log_likelihood', hint="use 'image' and / or 'label'")
 
 
-def _check(model, image, label, score, given, n_samples, chunk_rows):
+def _check(model, image, label, score, given, n_samples, chunk_rows, eps):
     """Every refusal, before anything is launched."""
     kind = getattr(model, 'KIND', None)
     if kind == 'celeba19':
@@ -51,14 +46,10 @@ def _check(model, image, label, score, given, n_samples, chunk_rows):
         if data[n] is None:
             raise ValueError('log_likelihood: `%s` is %s but no %s was passed'
                              % (n, ' and '.join(w for w, s in (('scored', score), ('given', given)) if n in s), n))
-    if int(n_samples) < 1:
-        raise ValueError('log_likelihood: n_samples must be at least 1 (got %r)' % (n_samples,))
-    if int(chunk_rows) < 1:
-        raise ValueError('log_likelihood: chunk_rows must be at least 1 (got %r)' % (chunk_rows,))
-    if not next(model.parameters()).is_cuda:
-        raise RuntimeError('log_likelihood: the model must live on the GPU (model.cuda()); the HIP path has no CPU '
-                           'fallback')
-    return kind, score, given
+    B = (image if image is not None else label).shape[0]
+    check_draws('log_likelihood', n_samples, chunk_rows, eps, B, model.n_latents)
+    require_gpu('log_likelihood', model)
+    return kind, score, given, B
 
 
 def _prepare(model, kind, image, label):
@@ -118,31 +109,20 @@ def score_rows(model, kind, z, image, label, score, bufs=None):
 
 def chunk_loop(model, kind, mu, logvar, image, label, score, n_samples, Kc, eps=None, seed=0):
     """draw -> decoders -> loss rows -> accumulate over chunks of ``Kc`` samples (the last may be shorter)."""
-    B, D = mu.shape
+    B = mu.shape[0]
     dev = mu.device
     Kc = min(int(Kc), int(n_samples))
-    z = torch.empty(Kc, B, D, dtype=torch.float32, device=dev)
-    lw = torch.empty(Kc, B, dtype=torch.float32, device=dev)
     L = 4 if kind == 'multimnist' else 1          # multimnist.model.max_length text positions per sample
     bufs = {'image': torch.empty(Kc * B, dtype=torch.float32, device=dev),
             'label': torch.empty(Kc * B * L, dtype=torch.float32, device=dev)}
-    state = torch.empty(B, 2, dtype=torch.float32, device=dev)
-    state[:, 0] = float('-inf')
-    state[:, 1] = 0.0
+    state = fresh_state(1, B, dev)[0]
     out = torch.empty(B, dtype=torch.float32, device=dev)
-    counter = torch.zeros(1, dtype=torch.int64, device=dev) if eps is None else None
     fed = []
-    for c, k0 in enumerate(range(0, n_samples, Kc)):
-        n = min(Kc, n_samples - k0)
-        zc, lwc = z[:n], lw[:n]
-        if eps is not None:
-            K.iw_draw(mu, logvar, zc, lwc, eps=eps[k0:k0 + n].to(dev).float().contiguous())
-        else:
-            K.iw_draw(mu, logvar, zc, lwc, seed=seed, counter_dev=counter, counter_offset=c)
+    for zc, lwc, finish_k in draw_chunks(mu, logvar, n_samples, Kc, eps=eps, seed=seed):
         terms = score_rows(model, kind, zc, image, label, score, bufs)
         if kind == 'multimnist' and 'label' in score:
             fed.append(model.text_decoder.last_fed)
-        K.iw_accumulate(lwc, terms, state, out, finish_k=n_samples if k0 + n == n_samples else 0)
+        K.iw_accumulate(lwc, terms, state, out, finish_k=finish_k)
     if fed:
         model.text_decoder.last_fed = torch.cat(fed, dim=1)      # [4, K * B], sample-major like z
     return out
@@ -159,25 +139,12 @@ def log_likelihood(model, image=None, label=None, score=('image',), given=('imag
     statistics, no Dropout) and every module's mode is restored afterwards; nothing in the model is modified.  After a
     MultiMNIST call that scores the text, ``model.text_decoder.last_fed`` holds the fed-back characters of all
     ``K * B`` rows ([4, K * B], sample-major)."""
-    kind, score, given = _check(model, image, label, score, given, n_samples, chunk_rows)
-    n_samples = int(n_samples)
+    kind, score, given, B = _check(model, image, label, score, given, n_samples, chunk_rows, eps)
     image, label = _prepare(model, kind, image, label)
-    B = (image if image is not None else label).shape[0]
-    D = model.n_latents
-    if eps is not None:
-        if tuple(eps.shape) != (n_samples, B, D):
-            raise ValueError('log_likelihood: eps must be [n_samples, B, D] = %s, got %s'
-                             % ((n_samples, B, D), tuple(eps.shape)))
-    modes = [(m, m.training) for m in model.modules()]
-    model.eval()
-    try:
-        with torch.no_grad():
-            mu, logvar = infer(model, kind, image, label, given)
-            return chunk_loop(model, kind, mu, logvar, image, label, score, n_samples, max(1, int(chunk_rows) // B),
-                              eps=eps, seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
-    finally:
-        for m, mode in modes:
-            m.training = mode
+    with eval_mode(model):
+        mu, logvar = infer(model, kind, image, label, given)
+        return chunk_loop(model, kind, mu, logvar, image, label, score, int(n_samples), max(1, int(chunk_rows) // B),
+                          eps=eps, seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
 
 
 # ----------------------------------------------------------------------------- the loglike.py drop-ins
@@ -241,9 +208,5 @@ def main(kind, load_checkpoint, image_shape):
         vals.append(log_likelihood(model, image[i:i + args.batch_size], label[i:i + args.batch_size], score=score,
                                    given=given, n_samples=args.n_samples, chunk_rows=args.chunk_rows,
                                    seed=args.seed + i).double().cpu())
-    vals = torch.cat(vals)
-    n = vals.numel()
-    sem = (vals.std(unbiased=True) / n ** 0.5).item() if n > 1 else float('nan')
-    print('log p(%s | q(z|%s)): mean %.4f  standard error %.4f  (N = %d data, K = %d samples)'
-          % (','.join(score), ','.join(given), vals.mean().item(), sem, n, args.n_samples))
+    report(','.join(score), torch.cat(vals), given, args.n_samples)
     return 0

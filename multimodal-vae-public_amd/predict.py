@@ -30,6 +30,8 @@ csrc/predict.hip: one streaming (maximum, sum) state per (datum, class)); then o
 import torch
 
 from . import kernels as K
+from . import loglike
+from .draws import draw_chunks, eval_mode, require_gpu
 
 KINDS = ('mnist', 'fashionmnist', 'celeba', 'celeba19', 'multimnist')
 MODES = {'mnist': 'categorical', 'fashionmnist': 'categorical', 'multimnist': 'categorical', 'celeba': 'bernoulli',
@@ -108,8 +110,7 @@ def _check(who, model, image, label, given, n_samples, chunk_rows, eps, confusio
         want = (C, 2, 2) if MODES[kind] == 'bernoulli' else (C, C)
         if confusion.dtype != torch.int64 or tuple(confusion.shape) != want or not confusion.is_cuda:
             raise ValueError('%s: confusion must be an int64 %s tensor on the GPU' % (who, want))
-    if not next(model.parameters()).is_cuda:
-        raise RuntimeError('%s: the model must live on the GPU (model.cuda()); the HIP path has no CPU fallback' % who)
+    require_gpu(who, model)
     return kind, given, B
 
 
@@ -118,10 +119,7 @@ def _infer(model, kind, image, label, given):
     if kind == 'celeba19':
         from .celeba19 import loglike as C19
         return C19.infer(model, image, label, given)
-    img = image if 'image' in given else None
-    lbl = label if 'label' in given else None
-    mu, logvar = model.infer(image=img, attrs=lbl) if kind == 'celeba' else model.infer(image=img, text=lbl)
-    return mu.contiguous(), logvar.contiguous()
+    return loglike.infer(model, kind, image, label, given)
 
 
 class LabelHead(object):
@@ -172,18 +170,8 @@ def fold_chunks(head, mode, mu, logvar, n_samples, Kc, eps=None, seed=0):
     if n_samples == 0:
         fold(head.logits(mu), 1)
         return out
-    Kc = min(int(Kc), int(n_samples))
-    z = torch.empty(Kc, B, D, dtype=torch.float32, device=dev)
-    lw = torch.empty(Kc, B, dtype=torch.float32, device=dev)            # the draw's density-ratio rows: not used here
-    counter = torch.zeros(1, dtype=torch.int64, device=dev) if eps is None else None
-    for c, k0 in enumerate(range(0, n_samples, Kc)):
-        n = min(Kc, n_samples - k0)
-        zc, lwc = z[:n], lw[:n]
-        if eps is not None:
-            K.iw_draw(mu, logvar, zc, lwc, eps=eps[k0:k0 + n].to(dev).float().contiguous())
-        else:
-            K.iw_draw(mu, logvar, zc, lwc, seed=seed, counter_dev=counter, counter_offset=c)
-        fold(head.logits(zc.view(n * B, D)), n_samples if k0 + n == n_samples else 0)
+    for zc, _, finish_k in draw_chunks(mu, logvar, n_samples, Kc, eps=eps, seed=seed):      # the density ratio is not used
+        fold(head.logits(zc.view(-1, D)), finish_k)
     return out
 
 
@@ -224,31 +212,25 @@ def _run(who, model, image, label, given, n_samples, chunk_rows, eps, seed, conf
         label = label.to(dev)
         label = label.float().contiguous() if mode == 'bernoulli' else label.long().contiguous()
     Kc = max(1, int(chunk_rows) // B)
-    modes = [(m, m.training) for m in model.modules()]
-    model.eval()
-    try:
-        with torch.no_grad():
-            mu, logvar = _infer(model, kind, image, label, given)
-            head = LabelHead(model, kind, B * max(1, min(Kc, n_samples)), dev)
-            out = fold_chunks(head, mode, mu, logvar, n_samples, Kc, eps=eps, seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
-            if head.fed:
-                model.text_decoder.last_fed = torch.cat(head.fed, dim=1)          # [4, K * B], sample-major like z
-            shape = (out.shape[0],) if mode == 'categorical' else tuple(out.shape[:2])
-            pred = torch.empty(shape, dtype=torch.int64, device=dev)
-            nll = correct = None
-            if score:
-                nll = torch.empty(shape, dtype=torch.float32, device=dev)
-                correct = torch.empty(shape, dtype=torch.uint8, device=dev)
-                if confusion is None:
-                    C = out.shape[1]
-                    confusion = torch.zeros((C, C) if mode == 'categorical' else (C, 2, 2), dtype=torch.int64, device=dev)
-                K.predict_score(out, mode, pred, targets=label.reshape(-1) if mode == 'categorical' else label, nll=nll,
-                                correct=correct, confusion=confusion)
-            else:
-                K.predict_score(out, mode, pred)
-    finally:
-        for m, training in modes:
-            m.training = training
+    with eval_mode(model):
+        mu, logvar = _infer(model, kind, image, label, given)
+        head = LabelHead(model, kind, B * max(1, min(Kc, n_samples)), dev)
+        out = fold_chunks(head, mode, mu, logvar, n_samples, Kc, eps=eps, seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
+        if head.fed:
+            model.text_decoder.last_fed = torch.cat(head.fed, dim=1)          # [4, K * B], sample-major like z
+        shape = (out.shape[0],) if mode == 'categorical' else tuple(out.shape[:2])
+        pred = torch.empty(shape, dtype=torch.int64, device=dev)
+        nll = correct = None
+        if score:
+            nll = torch.empty(shape, dtype=torch.float32, device=dev)
+            correct = torch.empty(shape, dtype=torch.uint8, device=dev)
+            if confusion is None:
+                C = out.shape[1]
+                confusion = torch.zeros((C, C) if mode == 'categorical' else (C, 2, 2), dtype=torch.int64, device=dev)
+            K.predict_score(out, mode, pred, targets=label.reshape(-1) if mode == 'categorical' else label, nll=nll,
+                            correct=correct, confusion=confusion)
+        else:
+            K.predict_score(out, mode, pred)
     if mode == 'bernoulli':
         res = {'logp': out[..., 0], 'logp0': out[..., 1], 'pred': pred}
     elif kind == 'multimnist':
@@ -344,7 +326,6 @@ def main(kind, load_checkpoint, image_shape, argv=None):
     and written to ``predict.txt`` under --out-dir."""
     import argparse
     import os
-    from .loglike import load_data
     parser = argparse.ArgumentParser()
     add_flags(parser)
     if kind in ('celeba', 'celeba19'):
@@ -355,7 +336,7 @@ def main(kind, load_checkpoint, image_shape, argv=None):
         raise SystemExit('this drop-in predicts with HIP kernels: pass --cuda on a ROCm GPU box')
     model = load_checkpoint(args.model_path, use_cuda=True)
     model.cuda().eval()
-    image, label = load_data('celeba' if kind == 'celeba19' else kind, args, image_shape)
+    image, label = loglike.load_data('celeba' if kind == 'celeba19' else kind, args, image_shape)
     if image.shape[0] < 1:
         raise SystemExit('no data to evaluate')
     nll, correct, confusion, exact = [], [], None, []

@@ -38,6 +38,7 @@ if __package__ in (None, ''):      # executed as a script (`python vision/loglik
 import torch  # noqa: E402
 
 from .. import kernels as K  # noqa: E402
+from ..draws import check_draws, draw_chunks, eval_mode, fresh_state, names, report, require_gpu  # noqa: E402,F401
 from .model import MODALITIES, N_CHANNELS  # noqa: E402
 
 PATHS = ('fused', 'rows')
@@ -47,16 +48,7 @@ BYTES_PER_ROW = 4 * 64 * 64 * sum(N_CHANNELS.values())      # 196,608: the six d
 
 
 def _names(value, what, default):
-    if value is None:
-        value = default
-    names = (value,) if isinstance(value, str) else tuple(value)
-    for n in names:
-        if n not in MODALITIES:
-            raise ValueError('vision log_likelihood: unknown modality %r in `%s` (the modalities are %s)'
-                             % (n, what, ', '.join(MODALITIES)))
-    if not names:
-        raise ValueError('vision log_likelihood: `%s` must name at least one modality' % what)
-    return tuple(m for m in MODALITIES if m in names)
+    return names(value, what, MODALITIES, 'vision log_likelihood', default=default)
 
 
 def _check(model, data, score, given, n_samples, chunk_rows, eps, path):
@@ -81,28 +73,13 @@ def _check(model, data, score, given, n_samples, chunk_rows, eps, path):
         if B is not None and x.shape[0] != B:
             raise ValueError('vision log_likelihood: `%s` holds %d data, the others %d' % (n, x.shape[0], B))
         B = x.shape[0]
-    if int(n_samples) < 1:
-        raise ValueError('vision log_likelihood: n_samples must be at least 1 (got %r)' % (n_samples,))
-    if int(chunk_rows) < 1:
-        raise ValueError('vision log_likelihood: chunk_rows must be at least 1 (got %r)' % (chunk_rows,))
-    if eps is not None and tuple(eps.shape) != (int(n_samples), B, model.n_latents):
-        raise ValueError('vision log_likelihood: eps must be [n_samples, B, D] = %s, got %s'
-                         % ((int(n_samples), B, model.n_latents), tuple(eps.shape)))
+    check_draws('vision log_likelihood', n_samples, chunk_rows, eps, B, model.n_latents)
     if path is None:
         path = DEFAULT_PATH
     if path not in PATHS:
         raise ValueError('vision log_likelihood: path must be one of %s, got %r' % (', '.join(PATHS), path))
-    if not next(model.parameters()).is_cuda:
-        raise RuntimeError('vision log_likelihood: the model must live on the GPU (model.cuda()); the HIP path has no '
-                           'CPU fallback')
+    require_gpu('vision log_likelihood', model)
     return score, given, path, B
-
-
-def fresh_state(n_states, B, device):
-    """[n_states, B, 2]: (running maximum, running sum) = (-inf, 0)."""
-    state = torch.zeros(n_states, B, 2, dtype=torch.float32, device=device)
-    state[:, :, 0] = float('-inf')
-    return state
 
 
 def score_fused(lw, segs, state, out, finish_k, rows=None):
@@ -135,23 +112,15 @@ def chunk_loop(model, mu, logvar, targets, score, n_samples, Kc, eps=None, seed=
     dev = mu.device
     S = len(score)
     Kc = min(int(Kc), int(n_samples))
-    z = torch.empty(Kc, B, D, dtype=torch.float32, device=dev)
-    lw = torch.empty(Kc, B, dtype=torch.float32, device=dev)
     rows = torch.empty(S, Kc * B, dtype=torch.float32, device=dev) if path == 'rows' else None
     state = fresh_state(S + 1, B, dev)
     out = torch.empty(S + 1, B, dtype=torch.float32, device=dev)
-    counter = torch.zeros(1, dtype=torch.int64, device=dev) if eps is None else None
     scorer = SCORERS[path]
-    for c, k0 in enumerate(range(0, n_samples, Kc)):
-        n = min(Kc, n_samples - k0)
-        zc, lwc = z[:n], lw[:n]
-        if eps is not None:
-            K.iw_draw(mu, logvar, zc, lwc, eps=eps[k0:k0 + n].to(dev).float().contiguous())
-        else:
-            K.iw_draw(mu, logvar, zc, lwc, seed=seed, counter_dev=counter, counter_offset=c)
-        zr = zc.view(n * B, D)
-        segs = [(getattr(model, name + '_decoder')(zr).reshape(n * B, -1).contiguous(), targets[name]) for name in score]
-        scorer(lwc, segs, state, out, n_samples if k0 + n == n_samples else 0, rows)
+    for zc, lwc, finish_k in draw_chunks(mu, logvar, n_samples, Kc, eps=eps, seed=seed):
+        R = lwc.numel()
+        zr = zc.view(R, D)
+        segs = [(getattr(model, name + '_decoder')(zr).reshape(R, -1).contiguous(), targets[name]) for name in score]
+        scorer(lwc, segs, state, out, finish_k, rows)
     return out
 
 
@@ -172,17 +141,10 @@ def log_likelihood(model, data, score=None, given=None, n_samples=1000, chunk_ro
     n_samples = int(n_samples)
     dev = next(model.parameters()).device
     x = {n: data[n].to(dev).float().contiguous() for n in set(score + given)}
-    modes = [(m, m.training) for m in model.modules()]
-    model.eval()
-    try:
-        with torch.no_grad():
-            mu, logvar = model.get_params(**{n: x[n] for n in given})
-            out = chunk_loop(model, mu.contiguous(), logvar.contiguous(), {n: x[n].reshape(B, -1) for n in score}, score,
-                             n_samples, max(1, int(chunk_rows) // B), eps=eps, seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
-                             path=path)
-    finally:
-        for m, mode in modes:
-            m.training = mode
+    with eval_mode(model):
+        mu, logvar = model.get_params(**{n: x[n] for n in given})
+        out = chunk_loop(model, mu.contiguous(), logvar.contiguous(), {n: x[n].reshape(B, -1) for n in score}, score,
+                         n_samples, max(1, int(chunk_rows) // B), eps=eps, seed=int(seed) & 0xFFFFFFFFFFFFFFFF, path=path)
     if not per_modality:
         return out[len(score)]
     res = {name: out[i] for i, name in enumerate(score)}
@@ -234,13 +196,6 @@ def batches(args, device):
     for batch in CelebVisionLoader('val', args.data_dir, args.batch_size, False, device,
                                    watermark_path=args.watermark_file, edge=args.edge):
         yield batch
-
-
-def report(name, vals, given, n_samples):
-    n = vals.numel()
-    sem = (vals.std(unbiased=True) / n ** 0.5).item() if n > 1 else float('nan')
-    print('log p(%s | q(z|%s)): mean %.4f  standard error %.4f  (N = %d data, K = %d samples)'
-          % (name, ','.join(given), vals.mean().item(), sem, n, n_samples))
 
 
 def main(argv=None):
