@@ -1149,6 +1149,62 @@ int mvae_predict_score(const float *logp, int mode, const void *targets /* nulla
                        int64_t *confusion /* nullable */, mvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * K29 Ragged product of experts: the PoE of K8-K10 for a batch whose rows observe different modalities (weak
+ *     supervision; csrc/poe_ragged.hip).  The reference has no counterpart: its loop runs every term on every row
+ *     (mnist/train.py:197-218; the `is_paired` of multimnist/train.py:189 is a comment without code).
+ *   slot_dev   int32 [T, B]: the row of the COMPACT outputs that (term t, batch row b) owns, or -1 where the term is
+ *              not evaluated on the row.  mu / logvar / z are [R, D], kl is [R]; rows >= R are never written, and a
+ *              slot outside 0..R-1 counts as -1.  An inactive (t, b) costs nothing; a wave whose row has no active
+ *              term exits.
+ *   experts    expert e's head is compact as well: [n_rows[e], ld] (n_rows: HOST array of E ints; pointers of an
+ *              expert with no row may be NULL), and erow_dev int32 [E, B] gives batch row b's row in it, or -1.  erow
+ *              maps the rows that have expert e one-to-one onto 0..n_rows[e]-1; an entry outside counts as -1.  An
+ *              expert of masks[t] that a row lacks drops out of that row's product; an absent row is never read.
+ *   noise      dense [T, B, D], read at (t, b) (NULL: z = mu).  With draw != 0 it is WRITTEN instead: eps of (t, b, d)
+ *              is element (t * B + b) * D + d of the stream mvae_philox_fill(seed, *counter_dev + counter_offset) would
+ *              write -- the dense index, so a draw does not depend on which other rows are present and equals
+ *              mvae_poe_fwd_draw's at full presence.  The counter is not advanced.
+ *   bwd        dz / dmu / dlogvar [R, D] and dkl [R] (any may be NULL) -> the experts' compact gradient buffers
+ *              [n_rows[e], ldg].  EVERY element is written: zero where no active term contains the expert on that
+ *              row.  Fixed summation order, no atomics: the same bits every run.
+ *   Refused (MVAE_ERR_ARG): E outside 1..MVAE_MAX_EXPERTS, T outside 1..40, B or D <= 0, ld or ldg < D, R < 0,
+ *   n_rows[e] outside 0..B, a NULL table, a NULL head or gradient of an expert that has rows, draw without noise / z /
+ *   counter.  R == 0 (forward) and no expert row at all (backward) launch nothing.
+ * ------------------------------------------------------------------------------------ */
+int mvae_poe_ragged_fwd(const mvae_experts_t *experts, int ld, int E, const int *n_rows, const int *erow_dev,
+                        const uint32_t *masks_dev, int T, const int *slot_dev, int R,
+                        float *noise /* nullable */, int draw, uint64_t seed, const uint64_t *counter_dev,
+                        uint64_t counter_offset, float *mu, float *logvar, float *z /* nullable */,
+                        float *kl /* nullable */, int B, int D, int variant, mvae_stream_t stream);
+int mvae_poe_ragged_bwd(const mvae_experts_t *experts, int ld, int E, const int *n_rows, const int *erow_dev,
+                        const uint32_t *masks_dev, int T, const int *slot_dev, int R,
+                        const float *noise, const float *mu, const float *logvar,
+                        const float *dz, const float *dmu, const float *dlogvar, const float *dkl,
+                        const mvae_expert_grads_t *grads, int ldg, int B, int D, int variant, mvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * K30 The reconstruction row sums of K11 / K13 for compact logits rows that find their target through an index
+ *     (csrc/loss_ragged.hip): logits [R, P] (BCE) or [R, K] (CE), targets in batch order -- float [B, P] or int64 [B] --
+ *     and rowmap_dev int32 [R], the batch row of each logits row.
+ *       row[r] = coef[r] * loss(logits[r, :], target[rowmap[r]])   (coef_dev [R], NULL: 1)
+ *       dlogits[r, :] = coef[r] * d loss / d logits                (fwd: optional, in the same pass; bwd: drow_dev as coef)
+ *     No gathered copy of the targets is made and a target row no logits row maps to is never read.  A rowmap entry
+ *     outside 0..B-1, or a label outside 0..K-1, makes its row NaN and indexes nothing.  K <= 1024.
+ * ------------------------------------------------------------------------------------ */
+int mvae_bce_rows_indexed_fwd(const float *logits, const float *target, const int *rowmap_dev,
+                              const float *coef_dev /* nullable */, float *rowsum, float *dlogits /* nullable */,
+                              int R, int P, int B, mvae_stream_t stream);
+int mvae_bce_rows_indexed_bwd(const float *logits, const float *target, const int *rowmap_dev,
+                              const float *drow_dev /* nullable */, float *dlogits, int R, int P, int B,
+                              mvae_stream_t stream);
+int mvae_ce_rows_indexed_fwd(const float *logits, const int64_t *label, const int *rowmap_dev,
+                             const float *coef_dev /* nullable */, float *row, float *dlogits /* nullable */,
+                             int R, int K, int B, mvae_stream_t stream);
+int mvae_ce_rows_indexed_bwd(const float *logits, const int64_t *label, const int *rowmap_dev,
+                             const float *drow_dev /* nullable */, float *dlogits, int R, int K, int B,
+                             mvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * C1  Gradient exchange of data-parallel replicas -- RCCL over xGMI.
  *     The reference has NO counterpart: it is single-process, single-device (no DataParallel, no
  *     torch.distributed anywhere; README.md:47 `CUDA_VISIBLE_DEVICES=0`).  What this replaces is what N

@@ -17,6 +17,8 @@ hyphen) or ``importlib.import_module('multimodal-vae-public_amd')``.
     mvae_amd.predict.predict(model, image, given=, n_samples=)        the label the model predicts from the image
     mvae_amd.predict.evaluate(model, image, label, confusion=)        ... scored: nll, correct, confusion counts
                                                                       (also ``mvae_amd.predict_label`` / ``mvae_amd.evaluate``)
+    mvae_amd.partial.PartialStep(model, lambda_image, lambda_label)   weak supervision: a train step on rows that observe
+                                                                      only some modalities (mnist, fashionmnist)
 """
 from . import _lib, kernels, arena, layers, functional, base, engine, optim, parallel, graph  # noqa: F401
 from .graph import capture_step  # noqa: F401
@@ -24,8 +26,9 @@ from . import loglike  # noqa: F401
 from .loglike import log_likelihood  # noqa: F401
 from . import predict  # noqa: F401
 from .predict import predict as predict_label, evaluate  # noqa: F401  (``predict`` itself names the module)
+from . import partial  # noqa: F401
 from . import mnist, fashionmnist, celeba, celeba19  # noqa: F401
 
 __all__ = ['kernels', 'arena', 'layers', 'functional', 'base', 'engine', 'optim', 'parallel', 'graph', 'capture_step',
-           'loglike', 'log_likelihood', 'predict', 'predict_label', 'evaluate',
+           'loglike', 'log_likelihood', 'predict', 'predict_label', 'evaluate', 'partial',
            'mnist', 'fashionmnist', 'celeba', 'celeba19']

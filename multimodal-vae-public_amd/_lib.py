@@ -254,6 +254,16 @@ _SIGNATURES = {
     # K28: label prediction (the fold of one state per (datum, class), and the scoring against labels)
     'mvae_predict_fold': (c_int, [P, ctypes.c_longlong, ctypes.c_longlong, c_int, c_int, c_int, c_int, P, P, c_int, P]),
     'mvae_predict_score': (c_int, [P, c_int, P, c_int, c_int, c_int, P, P, P, P, P]),
+    # K29: the PoE of a batch whose rows observe different modalities (compact experts and outputs behind index tables)
+    'mvae_poe_ragged_fwd': (c_int, [ctypes.POINTER(Experts), c_int, c_int, ctypes.POINTER(c_int), P, P, c_int, P, c_int,
+                                    P, c_int, c_uint64, P, c_uint64, P, P, P, P, c_int, c_int, c_int, P]),
+    'mvae_poe_ragged_bwd': (c_int, [ctypes.POINTER(Experts), c_int, c_int, ctypes.POINTER(c_int), P, P, c_int, P, c_int,
+                                    P, P, P, P, P, P, P, ctypes.POINTER(ExpertGrads), c_int, c_int, c_int, c_int, P]),
+    # K30: BCE / CE row sums of compact logits rows that find their target through a row map
+    'mvae_bce_rows_indexed_fwd': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, P]),
+    'mvae_bce_rows_indexed_bwd': (c_int, [P, P, P, P, P, c_int, c_int, c_int, P]),
+    'mvae_ce_rows_indexed_fwd': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, P]),
+    'mvae_ce_rows_indexed_bwd': (c_int, [P, P, P, P, P, c_int, c_int, c_int, P]),
     # C1: the gradient exchange (RCCL bound at run time)
     'mvae_comm_use_library': (c_int, [ctypes.c_char_p]),
     'mvae_comm_rccl_version': (c_int, []),

@@ -98,6 +98,53 @@ class PoEStackFn(torch.autograd.Function):
         return g_mu, g_lv, None
 
 
+class RaggedPoEFn(torch.autograd.Function):
+    """``PoEFn`` for a batch whose rows observe different modalities (csrc/poe_ragged.hip): ``heads_e`` is expert e's
+    COMPACT encoder output [n_e, 2D] -- one row per batch row that has the modality, None when no row has it -- and the
+    outputs mu, logvar, z [R, D] and kl [R] hold one row per active (term, batch row).  ``tables`` carries the device
+    index tables of ``partial.plan`` (``erow`` [E, B], ``masks`` [T], ``slot`` [T, B]) and the host numbers ``R``, ``B``.
+    ``noise`` is dense [T, B, D]: replayed, or with ``draw = (seed, counter_dev, counter_offset)`` written by the launch.
+    One launch forward, one backward; every element of every expert's gradient is written."""
+
+    @staticmethod
+    def forward(ctx, cfg, *heads):
+        tables, noise, draw, variant, D = cfg
+        live = [h for h in heads if h is not None]
+        dev = live[0].device if live else tables.slot.device
+        R = tables.R
+        mu = torch.empty(R, D, dtype=torch.float32, device=dev)
+        lv = torch.empty_like(mu)
+        z = torch.empty_like(mu)
+        kl = torch.empty(R, dtype=torch.float32, device=dev)
+        mus = [None if h is None else h[:, :D] for h in heads]
+        lvs = [None if h is None else h[:, D:] for h in heads]
+        K.poe_ragged_fwd(mus, lvs, tables.erow, tables.masks, tables.slot, R, noise, mu, lv, z, kl, variant, tables.B,
+                         draw=draw)
+        ctx.cfg = (tables, noise, variant, D)
+        ctx.none = [h is None for h in heads]
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(mu, lv, *live)
+        return mu, lv, z, kl
+
+    @staticmethod
+    def backward(ctx, dmu, dlv, dz, dkl):
+        tables, noise, variant, D = ctx.cfg
+        mu, lv = ctx.saved_tensors[:2]
+        live = iter(ctx.saved_tensors[2:])
+        heads = [None if absent else next(live) for absent in ctx.none]
+        grads = [None if h is None else torch.empty_like(h) for h in heads]
+
+        def halves(ts, lo, hi):
+            return [None if t is None else t[:, lo:hi] for t in ts]
+
+        def c(t):
+            return None if t is None else t.contiguous()
+        K.poe_ragged_bwd(halves(heads, 0, D), halves(heads, D, 2 * D), tables.erow, tables.masks, tables.slot, tables.R,
+                         noise, mu, lv, c(dz), c(dmu), c(dlv), c(dkl), halves(grads, 0, D), halves(grads, D, 2 * D),
+                         variant, tables.B)
+        return (None,) + tuple(grads)
+
+
 class ReparamFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mu, logvar, eps):
@@ -168,6 +215,76 @@ class _CeRowsFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         K.ce_bwd(x, y, g.contiguous(), dx, rows_per_group=1)
         return dx, None
+
+
+class BceRowsIndexedFn(torch.autograd.Function):
+    """rows[r] = coef[r] * sum_p bce(x[r, p], target[rowmap[r], p]): the image BCE of COMPACT logits rows whose targets
+    stay in batch order (csrc/loss_ragged.hip); ``coef`` [R] or None."""
+
+    @staticmethod
+    def forward(ctx, x, target, rowmap, coef):
+        x = x.contiguous()
+        rows = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+        K.bce_rows_indexed_fwd(x, target, rowmap, rows, coef=coef)
+        ctx.save_for_backward(x, target, rowmap, coef)
+        return rows
+
+    @staticmethod
+    def backward(ctx, g):
+        x, target, rowmap, coef = ctx.saved_tensors
+        dx = torch.empty_like(x)
+        K.bce_rows_indexed_bwd(x, target, rowmap, (g if coef is None else g * coef).contiguous(), dx)
+        return dx, None, None, None
+
+
+class CeRowsIndexedFn(torch.autograd.Function):
+    """rows[r] = coef[r] * -log_softmax(x[r, :] + 1e-6)[label[rowmap[r]]] for compact logits rows."""
+
+    @staticmethod
+    def forward(ctx, x, label, rowmap, coef):
+        x = x.contiguous()
+        rows = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+        K.ce_rows_indexed_fwd(x, label, rowmap, rows, coef=coef)
+        ctx.save_for_backward(x, label, rowmap, coef)
+        return rows
+
+    @staticmethod
+    def backward(ctx, g):
+        x, label, rowmap, coef = ctx.saved_tensors
+        dx = torch.empty_like(x)
+        K.ce_rows_indexed_bwd(x, label, rowmap, (g if coef is None else g * coef).contiguous(), dx)
+        return dx, None, None, None
+
+
+class RaggedTermSumsFn(torch.autograd.Function):
+    """The three ELBO terms of a ragged bimodal step and their total from its compact loss rows, which lie in the order
+    [image-only | joint | label-only] (``partial.plan``): ``bce_rows`` [n_img + n_joint] and ``ce_rows``
+    [n_joint + n_lbl] already carry their lambda / B, ``kl`` [R] is weighted by ``kl_coef`` ([1] device: beta / B) here.
+    Returns (total, [joint, image, label, total]); only the total is differentiable.  ``mvae_group_sums`` per segment,
+    accumulated in a fixed order; an empty term reads 0."""
+
+    @staticmethod
+    def forward(ctx, counts, kl_coef, bce_rows, ce_rows, kl):
+        n_img, n_joint, n_lbl = counts
+        out = torch.zeros(4, dtype=torch.float32, device=kl.device)
+        segs = ((0, n_joint, n_img, 0, n_img), (1, n_img, 0, None, 0), (2, n_lbl, None, n_joint, n_img + n_joint))
+        for t, n, b0, c0, k0 in segs:           # (reference term, rows, offsets into bce_rows / ce_rows / kl)
+            if n == 0:
+                continue
+            parts = [(bce_rows, b0, None), (ce_rows, c0, None), (kl, k0, kl_coef)]
+            for rows, lo, coef in parts:
+                if lo is not None:
+                    K.group_sums(rows[lo:lo + n], coef, out[t:t + 1], out[3:4], 1, n, accumulate=True)
+        ctx.kl_coef = kl_coef
+        ctx.lens = [None if r is None else r.numel() for r in (bce_rows, ce_rows, kl)]
+        ctx.mark_non_differentiable(out)
+        return out[3].clone(), out
+
+    @staticmethod
+    def backward(ctx, g, _):
+        nb, nc, nk = ctx.lens
+        return (None, None, None if nb is None else g.expand(nb), None if nc is None else g.expand(nc),
+                (g * ctx.kl_coef[0]).expand(nk))
 
 
 class _KlRowsFn(torch.autograd.Function):

@@ -843,6 +843,80 @@ def poe_bwd_split(mus, lvs, masks_dev, noise, mu, logvar, dz_a, slots_a, dz_b, s
                                         _lib.POE_VARIANT[variant], _stream()), 'mvae_poe_bwd_split')
 
 
+def _ragged_tables(mus, lvs, erow_dev, masks_dev, slot_dev, B):
+    """Checks shared by the ragged PoE launchers -> (Experts, ld, n_rows array).  ``mus`` / ``lvs`` hold None for an
+    expert no row has."""
+    E = len(mus)
+    if not 1 <= E <= _lib.MAX_EXPERTS or len(lvs) != E:
+        raise RuntimeError('1..%d experts' % _lib.MAX_EXPERTS)
+    live = [(m, v) for m, v in zip(mus, lvs) if m is not None and m.shape[0] > 0]
+    ld = _expert_ld([m for m, _ in live], [v for _, v in live])
+    for t, shape in ((erow_dev, (E, B)), (slot_dev, (masks_dev.numel(), B))):
+        _need_gpu(t)
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise RuntimeError('ragged PoE: index table must be contiguous int32 %s, got %s %s'
+                               % (shape, t.dtype, tuple(t.shape)))
+    _need_gpu(masks_dev)
+    ex = _lib.Experts()
+    n_rows = (ctypes.c_int * E)()
+    for e, (m, v) in enumerate(zip(mus, lvs)):
+        if m is None or m.shape[0] == 0:
+            continue
+        if v is None or v.shape != m.shape:
+            raise RuntimeError('ragged PoE: expert %d has mu %s and logvar %s' % (e, tuple(m.shape),
+                                                                                 None if v is None else tuple(v.shape)))
+        ex.mu[e], ex.logvar[e], n_rows[e] = m.data_ptr(), v.data_ptr(), m.shape[0]
+    return ex, ld, n_rows
+
+
+def poe_ragged_fwd(mus, lvs, erow_dev, masks_dev, slot_dev, R, noise, mu, logvar, z, kl, variant, B, draw=None):
+    """PoE on a batch whose rows have different experts (include/mvae_hip.h, K29).  mus/lvs: per-expert compact
+    [n_e, D] views (None: no row has the expert); erow_dev int32 [E, B]; slot_dev int32 [T, B]; outputs compact with at
+    least R rows.  noise dense [T, B, D] (read), or with ``draw = (seed, counter_dev, counter_offset)`` written."""
+    ex, ld, n_rows = _ragged_tables(mus, lvs, erow_dev, masks_dev, slot_dev, B)
+    _need_gpu(noise, mu, logvar, z, kl); _f32c(noise, mu, logvar, z, kl)
+    T, D = masks_dev.numel(), mu.shape[1]
+    for t, n in ((mu, R * D), (logvar, R * D), (z, R * D), (kl, R), (noise, T * B * D)):
+        if t is not None and t.numel() < n:
+            raise RuntimeError('ragged PoE: a buffer of %d elements where %d are needed' % (t.numel(), n))
+    if ld == 0:
+        ld = D          # no expert has a row: the prior alone
+    seed, counter_dev, counter_offset = draw if draw is not None else (0, None, 0)
+    _need_gpu(counter_dev)
+    check(_lib.lib().mvae_poe_ragged_fwd(ctypes.byref(ex), ld, len(mus), n_rows, _ptr(erow_dev), _ptr(masks_dev), T,
+                                         _ptr(slot_dev), int(R), _ptr(noise), 1 if draw is not None else 0, int(seed),
+                                         _ptr(counter_dev), int(counter_offset), _ptr(mu), _ptr(logvar), _ptr(z),
+                                         _ptr(kl), B, D, _lib.POE_VARIANT[variant], _stream()), 'mvae_poe_ragged_fwd')
+
+
+def poe_ragged_bwd(mus, lvs, erow_dev, masks_dev, slot_dev, R, noise, mu, logvar, dz, dmu, dlogvar, dkl, g_mus, g_lvs,
+                   variant, B):
+    """Backward of ``poe_ragged_fwd``: dz / dmu / dlogvar [R, D], dkl [R] (any None) -> every element of the experts'
+    compact gradient views g_mus / g_lvs (None where the expert has no row)."""
+    ex, ld, n_rows = _ragged_tables(mus, lvs, erow_dev, masks_dev, slot_dev, B)
+    live = [(m, v) for m, v in zip(g_mus, g_lvs) if m is not None and m.shape[0] > 0]
+    ldg = _expert_ld([m for m, _ in live], [v for _, v in live])
+    _need_gpu(noise, mu, logvar, dz, dmu, dlogvar, dkl); _f32c(noise, mu, logvar, dz, dmu, dlogvar, dkl)
+    T, D = masks_dev.numel(), mu.shape[1]
+    for t, n in ((mu, R * D), (logvar, R * D), (dz, R * D), (dmu, R * D), (dlogvar, R * D), (dkl, R),
+                 (noise, T * B * D)):
+        if t is not None and t.numel() < n:
+            raise RuntimeError('ragged PoE: a buffer of %d elements where %d are needed' % (t.numel(), n))
+    gr = _lib.ExpertGrads()
+    for e, (m, v) in enumerate(zip(g_mus, g_lvs)):
+        if n_rows[e] == 0:
+            continue
+        if m is None or v is None or m.shape[0] != n_rows[e] or v.shape != m.shape:
+            raise RuntimeError('ragged PoE: gradient views of expert %d do not match its %d rows' % (e, n_rows[e]))
+        gr.dmu[e], gr.dlogvar[e] = m.data_ptr(), v.data_ptr()
+    if ld == 0:
+        ld = ldg = D
+    check(_lib.lib().mvae_poe_ragged_bwd(ctypes.byref(ex), ld, len(mus), n_rows, _ptr(erow_dev), _ptr(masks_dev), T,
+                                         _ptr(slot_dev), int(R), _ptr(noise), _ptr(mu), _ptr(logvar), _ptr(dz),
+                                         _ptr(dmu), _ptr(dlogvar), _ptr(dkl), ctypes.byref(gr), ldg, B, D,
+                                         _lib.POE_VARIANT[variant], _stream()), 'mvae_poe_ragged_bwd')
+
+
 def kl_rows_fwd(mu, logvar, kl):
     _need_gpu(mu, logvar, kl); _f32c(mu, logvar, kl)
     check(_lib.lib().mvae_kl_rows_fwd(_ptr(mu), _ptr(logvar), _ptr(kl), mu.shape[0], mu.shape[1], _stream()),
@@ -948,6 +1022,63 @@ def ce_bwd(logits, label, drow, dlogits, rows_per_group=None, label_rows=None):
     check(_lib.lib().mvae_ce_bwd(_ptr(logits), _ptr(label), _ptr(drow), _ptr(dlogits), R, K,
                                  rows_per_group or R, label_rows or label.shape[0], _stream()),
           'mvae_ce_bwd')
+
+
+def _indexed_args(logits, target, rowmap, coef, out, dlogits, what):
+    """Shapes of the indexed row sums (include/mvae_hip.h, K30): logits [R, P], rowmap int32 [R], coef / out [R]."""
+    _need_gpu(logits, target, rowmap, coef, out, dlogits); _f32c(logits, coef, out, dlogits)
+    R = logits.shape[0]
+    if logits.dim() != 2 or rowmap.dtype != torch.int32 or not rowmap.is_contiguous() or rowmap.numel() != R or not \
+            target.is_contiguous():
+        raise RuntimeError('%s: logits [R, P], a contiguous int32 row map [R] and contiguous targets; got %s, %s %s'
+                           % (what, tuple(logits.shape), rowmap.dtype, tuple(rowmap.shape)))
+    for t in (coef, out):
+        if t is not None and t.numel() != R:
+            raise RuntimeError('%s: %d per-row values for %d rows' % (what, t.numel(), R))
+    if dlogits is not None and dlogits.shape != logits.shape:
+        raise RuntimeError('%s: dlogits %s for logits %s' % (what, tuple(dlogits.shape), tuple(logits.shape)))
+    return R
+
+
+def bce_rows_indexed_fwd(logits, target, rowmap, rowsum, coef=None, dlogits=None):
+    """rowsum[r] = coef[r] * sum_p bce(logits[r, p], target[rowmap[r], p]); target [B, P] in batch order; with
+    ``dlogits`` the gradient coef[r] * dbce/dx in the same pass."""
+    R = _indexed_args(logits, target, rowmap, coef, rowsum, dlogits, 'bce_rows_indexed_fwd')
+    _f32c(target)
+    if target.dim() != 2 or target.shape[1] != logits.shape[1]:
+        raise RuntimeError('bce_rows_indexed_fwd: target %s for logits %s' % (tuple(target.shape), tuple(logits.shape)))
+    check(_lib.lib().mvae_bce_rows_indexed_fwd(_ptr(logits), _ptr(target), _ptr(rowmap), _ptr(coef), _ptr(rowsum),
+                                               _ptr(dlogits), R, logits.shape[1], target.shape[0], _stream()),
+          'mvae_bce_rows_indexed_fwd')
+
+
+def bce_rows_indexed_bwd(logits, target, rowmap, drow, dlogits):
+    """dlogits[r, p] = drow[r] * dbce/dx (drow None: 1)."""
+    R = _indexed_args(logits, target, rowmap, drow, None, dlogits, 'bce_rows_indexed_bwd')
+    _f32c(target)
+    if target.dim() != 2 or target.shape[1] != logits.shape[1]:
+        raise RuntimeError('bce_rows_indexed_bwd: target %s for logits %s' % (tuple(target.shape), tuple(logits.shape)))
+    check(_lib.lib().mvae_bce_rows_indexed_bwd(_ptr(logits), _ptr(target), _ptr(rowmap), _ptr(drow), _ptr(dlogits), R,
+                                               logits.shape[1], target.shape[0], _stream()),
+          'mvae_bce_rows_indexed_bwd')
+
+
+def ce_rows_indexed_fwd(logits, label, rowmap, row, coef=None, dlogits=None):
+    """row[r] = coef[r] * -log_softmax(logits[r, :] + 1e-6)[label[rowmap[r]]]; label int64 [B] in batch order."""
+    R = _indexed_args(logits, label, rowmap, coef, row, dlogits, 'ce_rows_indexed_fwd')
+    if label.dtype != torch.int64 or label.dim() != 1:
+        raise RuntimeError('labels must be contiguous int64 [B]')
+    check(_lib.lib().mvae_ce_rows_indexed_fwd(_ptr(logits), _ptr(label), _ptr(rowmap), _ptr(coef), _ptr(row),
+                                              _ptr(dlogits), R, logits.shape[1], label.shape[0], _stream()),
+          'mvae_ce_rows_indexed_fwd')
+
+
+def ce_rows_indexed_bwd(logits, label, rowmap, drow, dlogits):
+    R = _indexed_args(logits, label, rowmap, drow, None, dlogits, 'ce_rows_indexed_bwd')
+    if label.dtype != torch.int64 or label.dim() != 1:
+        raise RuntimeError('labels must be contiguous int64 [B]')
+    check(_lib.lib().mvae_ce_rows_indexed_bwd(_ptr(logits), _ptr(label), _ptr(rowmap), _ptr(drow), _ptr(dlogits), R,
+                                              logits.shape[1], label.shape[0], _stream()), 'mvae_ce_rows_indexed_bwd')
 
 
 def group_sums(rows, coef, out, total, G, rows_per_group, accumulate=False):

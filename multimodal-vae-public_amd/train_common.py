@@ -97,6 +97,17 @@ def reference_parser(kind):
         parser.add_argument(flag, **kw)
     parser.add_argument('--cuda', action='store_true', default=False, help='enables CUDA training [default: False]')
     add_extra_flags(parser)
+    if kind in ('mnist', 'fashionmnist'):
+        # weak supervision (accuracy against the number of paired examples); the reference never shipped it
+        parser.add_argument('--n-paired', type=int, default=None, metavar='N',
+                            help='number of training examples that keep their pairing; the batches then run the ragged '
+                                 'step of partial.py (eager, single GPU) [default: None = every example, the fused step]')
+        parser.add_argument('--paired-seed', type=int, default=0, metavar='S',
+                            help='seed of the permutation that picks the paired examples, fixed over epochs [default: 0]')
+        parser.add_argument('--unpaired-labels', choices=('keep', 'drop'), default='keep',
+                            help="'keep': unpaired examples still feed the image-only and the label-only term, only the "
+                                 "joint term is off. 'drop': they carry no label (-1) and feed the image-only term alone "
+                                 "[default: keep]")
     if kind == 'celeba19':
         # SURVEY Appendix B-4, decided explicitly: every model() call of the reference runs the image decoder
         # (celeba19/model.py:52-61), also for the 18 attribute-only terms whose image output nobody reads
@@ -216,13 +227,20 @@ class IdxLoader(object):
         return (len(self.dataset) + self.batch_size - 1) // self.batch_size
 
     def __iter__(self):
+        for _, image, label in self.indexed():
+            yield image, label
+
+    def indexed(self):
+        """One epoch as (dataset indices of the batch -- int64, on the host --, image, label): for a consumer that keeps
+        per-example state by dataset index (the paired subset of ``--n-paired``)."""
         n_total = self._n_total
         order = torch.randperm(n_total, generator=self._gen) if self.shuffle else torch.arange(n_total)
-        order = shard_order(order, self.rank, self.world).to(self.device)
+        order_host = shard_order(order, self.rank, self.world)
+        order = order_host.to(self.device)
         n = order.numel()
         for i in range(0, n, self.batch_size):
             idx = order[i:i + self.batch_size]
-            yield self._to_tensor(self.images[idx]), self.labels[idx]
+            yield order_host[i:i + self.batch_size], self._to_tensor(self.images[idx]), self.labels[idx]
 
 
 def _find_idx(root, stem):
@@ -272,6 +290,10 @@ def run(kind, mvae_cls, test_total, args, lambda_label, annealing_epoch_offset=0
                          '(the CPU path is the reference itself)')
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
+    n_paired = getattr(args, 'n_paired', None)
+    if n_paired is not None and world > 1:
+        raise SystemExit('--n-paired runs the ragged step of partial.py, which is single-GPU: start one process '
+                         '(WORLD_SIZE is %d)' % world)
     device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', '0')))
     torch.cuda.set_device(device)
     if world > 1:
@@ -295,23 +317,45 @@ def run(kind, mvae_cls, test_total, args, lambda_label, annealing_epoch_offset=0
             return make_engine(model, args, rank, batch_size)
         return BimodalStep(model, batch_size, args.lambda_image, lambda_label, seed=1 + rank)
 
-    engine = build_engine(args.batch_size)
+    weak = subset = None
+    if n_paired is not None:
+        # weak supervision: only n_paired examples keep their pairing; every batch takes the eager ragged step
+        from .partial import PartialStep, batch_flags, paired_subset, synthetic_flags
+        subset = paired_subset(len(train_loader.dataset), n_paired, args.paired_seed)
+        weak = PartialStep(model, args.lambda_image, lambda_label, seed=1 + rank)
+    engine = build_engine(args.batch_size) if weak is None else None
     dp = DataParallel(model, engine) if world > 1 else None
     captured = [False]
     ragged = {}           # the reference trains on the loader's short last batch too: eager engine per size
+
+    def train_batches():
+        """(dataset indices of the batch on the host, image, label); the indices only where the paired subset needs them."""
+        if weak is not None and not args.synthetic:
+            return train_loader.indexed()
+        return ((None, image, label) for image, label in train_loader)
 
     def train(epoch):
         model.train()
         train_loss_meter = AverageMeter()
         pending = []          # device-side losses; read back only at the log interval
-        for batch_idx, (image, label) in enumerate(train_loader):
+        for batch_idx, (index, image, label) in enumerate(train_batches()):
             if epoch < args.annealing_epochs:
                 annealing_factor = (float(batch_idx + (epoch - 1 + annealing_epoch_offset) * N_mini_batches + 1) /
                                     float(args.annealing_epochs * N_mini_batches))
             else:
                 annealing_factor = 1.0
             image, label = image.to(device), label.to(device)
-            if len(image) != args.batch_size:
+            if weak is not None:
+                if args.synthetic:
+                    is_paired = synthetic_flags(len(image), n_paired / float(subset.size), args.paired_seed, batch_idx)
+                else:
+                    is_paired = subset[index.numpy()]
+                present, paired = batch_flags(is_paired, args.unpaired_labels)
+                if args.unpaired_labels == 'drop':        # true missing data: the label of an unpaired row is gone
+                    label = label.masked_fill(torch.from_numpy(~is_paired).to(device), -1)
+                elbo = weak.step(image, label, annealing_factor, present=present, paired=paired)
+                optimizer.step()
+            elif len(image) != args.batch_size:
                 eng = ragged.get(len(image))
                 if eng is None:
                     eng = ragged[len(image)] = build_engine(len(image))
